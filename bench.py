@@ -8,7 +8,7 @@ table is already resident in HBM:   clear -> BAM->Hansel fill -> 100 x {path ext
 Workload at every N: BASELINE.json config C3, one 10k-SNP / 1M-read / k=5 (L=5) contig PER GPU
 (seed = rank): independent windows, weak scaling, results gathered to rank 0 over RCCL.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--paths 100]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--paths 100] [--dump-outputs DIR]
 
 Prints ONE JSON line (rank 0).  `value` = haplotypes/s over all ranks.
 """
@@ -61,7 +61,42 @@ def parse():
     ap.add_argument("--dump-gathered", default="", help="rank 0 writes what it gathered in the last timed step (every rank's paths and "
                     "records) to this .npz -- the tests compare it with the oracle, rank by rank")
     ap.add_argument("--share-gpu", action="store_true", help="ranks take GPU (rank mod visible GPUs) instead of one each (gloo only)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the timed path returned in its last step as DIR/<name>.npy (float32 / float64, at most "
+                         "64 MB in all: a seeded sample of the path rows beyond that) -- two builds compared output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BYTES = 64 << 20      # --dump-outputs: the most it writes
+DUMP_SEED = 20240917       # ... and the seed of the row sample it takes when the paths alone would exceed that
+
+
+def dump_outputs(dirn, res, stats=None):
+    """--dump-outputs: the result records of the last timed step (`res`: one dict of Hansel.spin, or the list of HanselBatch.spin,
+    windows one after the other) as DIR/<name>.npy.  Path symbols (0..6) go as float32, everything else as float64.  When the
+    paths would take the writes over DUMP_BYTES, a fixed seeded sample of their rows is written, with its row numbers in paths_rows."""
+    rs = res if isinstance(res, list) else [res]
+    out = {"n": np.array([r["n"] for r in rs], dtype=np.float64),
+           "hole_at": np.array([r["hole_at"] for r in rs], dtype=np.float64)}
+    for k in ("hp_current", "hp_original", "ratio", "magnitude", "min_marginal"):
+        out[k] = np.concatenate([np.asarray(r[k], dtype=np.float64).reshape(-1) for r in rs])
+    if stats is not None:
+        out["fill_stats"] = np.asarray(tuple(stats), dtype=np.float64)
+    paths = np.concatenate([np.asarray(r["paths"]) for r in rs])
+    room = DUMP_BYTES - sum(a.nbytes for a in out.values())
+    row_bytes = max(1, paths.shape[1]) * 4
+    if paths.shape[0] * row_bytes > room:
+        keep = max(0, (room - 8 * paths.shape[0]) // row_bytes)
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(paths.shape[0], size=keep, replace=False))
+        out["paths_rows"] = rows.astype(np.float64)
+        paths = paths[rows]
+    out["paths"] = paths.astype(np.float32)
+    os.makedirs(dirn, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(dirn, k + ".npy"), a)
 
 
 def self_launch(args):
@@ -411,6 +446,8 @@ def bench_batch(args, cfg_name, paths, desc, rank, world, local, dev):
         n_paths += sum(r["n"] for r in res)
     fence()
     dt = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res)
     tt = torch.tensor([dt, float(n_paths)], dtype=torch.float64, device=dev)
     if world > 1:
         tmax = tt.clone(); dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -537,6 +574,8 @@ def main():
         n_paths_local += res["n"]
     fence()
     dt = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, stats)
     if ex is not None:
         gathered = drained.get("last")                  # the last timed step's records, every rank's (rank 0)
     prof = h.profile_get()

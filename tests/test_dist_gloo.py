@@ -1,4 +1,4 @@
-"""The N>1 path (descriptor broadcast, window ownership, result gather) with world_size 2
+"""The N>1 path (descriptor broadcast, window ownership, result gather) with world_size 2 and 8
 over gloo on CPU.  The records travel as tensors exactly as they do over RCCL."""
 import os
 import socket
@@ -39,7 +39,7 @@ WORKER = textwrap.dedent('''
     d = gdist.broadcast_descriptor(dict(paths=4, steps=2, warmup=1, config=3) if rank == 0 else {}, dev, world, rank)
     assert d == dict(paths=4, steps=2, warmup=1, config=3), d
     rng = np.random.default_rng(rank)
-    k = 2 + rank
+    k = 2 + rank %% 3
     res = dict(n=k, hole_at=rank * 5, paths=rng.integers(0, 7, (k, 9), dtype=np.uint8), hp_current=rng.random(k),
                hp_original=rng.random(k), ratio=rng.random(k), magnitude=rng.random(k))
     got = gdist.gather_results(res, 8, d["paths"], dev, world, rank)
@@ -47,7 +47,7 @@ WORKER = textwrap.dedent('''
         assert len(got) == world
         for r in range(world):
             rr = np.random.default_rng(r)
-            kk = 2 + r
+            kk = 2 + r %% 3
             assert got[r]["n"] == kk and got[r]["hole_at"] == r * 5
             assert np.array_equal(got[r]["paths"], rr.integers(0, 7, (kk, 9), dtype=np.uint8))
             assert np.array_equal(got[r]["hp_current"], rr.random(kk))
@@ -104,7 +104,7 @@ EX_WORKER = textwrap.dedent('''
 ''')
 
 
-def _run_world2(tmp_path, text, marker):
+def _run_world(tmp_path, text, marker, world=2):
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
@@ -112,8 +112,10 @@ def _run_world2(tmp_path, text, marker):
     script = tmp_path / "w.py"
     script.write_text(text)
     procs = []
-    for r in range(2):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    for r in range(world):
+        # (the workers run on the CPU: they are kept away from any GPU the box has)
+        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
+                   HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="")
         procs.append(subprocess.Popen([sys.executable, str(script)], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
     outs = [p.communicate(timeout=120)[0].decode() for p in procs]
     assert all(p.returncode == 0 for p in procs), outs
@@ -122,7 +124,12 @@ def _run_world2(tmp_path, text, marker):
 
 def test_overlapped_exchange_world2(tmp_path):
     # ResultExchange: five steps through two slots, every step's records of both ranks arrive on rank 0, in step order, one step late
-    _run_world2(tmp_path, EX_WORKER % ROOT, "EXCHANGE_OK")
+    _run_world(tmp_path, EX_WORKER % ROOT, "EXCHANGE_OK")
+
+
+def test_overlapped_exchange_world8(tmp_path):
+    # the same at world = 8 (BASELINE config C4: one rank per GPU of a node): eight records per step reach rank 0
+    _run_world(tmp_path, EX_WORKER % ROOT, "EXCHANGE_OK", world=8)
 
 
 def test_exchange_with_one_rank_needs_no_process_group():
@@ -154,6 +161,11 @@ def test_broadcast_and_gather_world2(tmp_path):
     outs = [p.communicate(timeout=120)[0].decode() for p in procs]
     assert all(p.returncode == 0 for p in procs), outs
     assert "GATHER_OK" in outs[0]
+
+
+def test_broadcast_and_gather_world8(tmp_path):
+    # the descriptor broadcast and the blocking gather at world = 8
+    _run_world(tmp_path, WORKER % ROOT, "GATHER_OK", world=8)
 
 
 def test_bench_launches_its_own_ranks_without_a_launcher():
