@@ -133,8 +133,12 @@ def _add_path(paths, i, key, hansel_path, hp_current, hp_original, magnitude):
 def recover(hansel, n_snps, max_paths, log=None):
     """cmd.py:148-179 on the device; returns the PATHS table in order of discovery.  The spins have already
     happened when the notes are written, but the notes are the reference's, in the reference's order."""
+    return paths_of_spin(hansel, hansel.spin(max_paths, MIN_REMOVE), log)
+
+
+def paths_of_spin(hansel, res, log=None):
+    """The PATHS table of cmd.py:148-179 from a finished spin `res` (Hansel.spin's dict, or a panel's for this window)."""
     log = log or sys.stderr
-    res = hansel.spin(max_paths, MIN_REMOVE)
     paths = {}
     for i in range(res["n"]):
         log.write("[NOTE] *Establishing next path\n")                                   # gretel.py:142

@@ -27,6 +27,7 @@
 #include <cstring>
 #include <atomic>
 #include <chrono>
+#include <map>
 #include <mutex>
 #include <new>
 #include <string>
@@ -2381,6 +2382,12 @@ struct gh_batch {
     size_t pused[2];
     int prof_windows;
     double prof_bytes[2];
+    // panels (gh_panel_*): windows that differ in N, W and L.  N, W above are then the largest window's; d_wd holds 2n descriptors
+    // (every window's, and the lists the pipeline launches take); the pipeline's paths are [window][max_paths][N_w + 1] in p_paths
+    bool panel;
+    uint8_t *p_paths;
+    size_t p_pcap;
+    int pinfo_nt, pinfo_c;      // the last gh_panel_spin: threads and chunk of the pipeline launch over the most windows
 };
 
 extern "C" int gh_batch_destroy(gh_batch_t *b)
@@ -2388,7 +2395,7 @@ extern "C" int gh_batch_destroy(gh_batch_t *b)
     if (!b) return GH_OK;
     hipSetDevice(b->dev);
     if (b->stream) hipStreamSynchronize(b->stream);
-    hipFree(b->d_wd); hipFree(b->d_states); hipFree(b->d_paths); hipFree(b->d_recs); hipFree(b->d_partial);
+    hipFree(b->d_wd); hipFree(b->d_states); hipFree(b->d_paths); hipFree(b->d_recs); hipFree(b->d_partial); hipFree(b->p_paths);
     for (int g = 0; g < 3; g++) {
         if (b->gstream[g]) { hipStreamSynchronize(b->gstream[g]); hipStreamDestroy(b->gstream[g]); }
         if (b->gevent[g]) hipEventDestroy(b->gevent[g]);
@@ -2400,39 +2407,47 @@ extern "C" int gh_batch_destroy(gh_batch_t *b)
     return GH_OK;
 }
 
-extern "C" int gh_batch_create(gh_t **handles, int n, gh_batch_t **out)
+// gh_batch_create / gh_panel_create: a panel's windows may differ in N and W (and in L, gh_panel_spin)
+static int batch_create(gh_t **handles, int n, gh_batch_t **out, bool panel)
 {
     if (!handles || n < 1 || !out) return fail(GH_ERR_ARG, "bad argument");
     gh_handle *h0 = handles[0];
+    int maxN = 0, maxW = 0;
     for (int w = 0; w < n; w++) {
         gh_handle *h = handles[w];
         if (!h) return fail(GH_ERR_ARG, "null handle at %d", w);
-        if (h->N != h0->N || h->W != h0->W || h->dev != h0->dev || h->cfg.storage != h0->cfg.storage ||
+        if ((!panel && (h->N != h0->N || h->W != h0->W)) || h->dev != h0->dev || h->cfg.storage != h0->cfg.storage ||
             h->cfg.cond_mode != h0->cfg.cond_mode || h->cfg.marginal_term != h0->cfg.marginal_term ||
             h->cfg.offer_zero != h0->cfg.offer_zero || memcmp(h->cfg.cand_order, h0->cfg.cand_order, 5) != 0)
-            return fail(GH_ERR_ARG, "window %d differs from window 0 in shape, storage, mode or device", w);
+            return fail(GH_ERR_ARG, panel ? "window %d differs from window 0 in storage, mode or device"
+                                          : "window %d differs from window 0 in shape, storage, mode or device", w);
         for (int v = 0; v < w; v++)
             if (handles[v] == h) return fail(GH_ERR_ARG, "window %d is the same handle as window %d", w, v);
+        if (h->N > maxN) maxN = h->N;
+        if (h->W > maxW) maxW = h->W;
     }
     HIPCHK(hipSetDevice(h0->dev));
     gh_batch *b = new (std::nothrow) gh_batch();
     if (!b) return fail(GH_ERR_NOMEM, "host allocation failed");
-    b->n = n; b->dev = h0->dev; b->N = h0->N; b->W = h0->W; b->L = 0;
+    b->n = n; b->dev = h0->dev; b->N = maxN; b->W = maxW; b->L = 0;
     b->hs.assign(handles, handles + n);
     b->stream = nullptr; b->d_wd = nullptr; b->d_states = nullptr; b->d_paths = nullptr; b->d_recs = nullptr; b->d_partial = nullptr;
     for (int g = 0; g < 3; g++) { b->gstream[g] = nullptr; b->gevent[g] = nullptr; }
     b->cap_paths = 0;
     b->pipe_windows = b->pipe_aborted = 0;
     b->prof_every = 0; b->pused[0] = b->pused[1] = 0; b->prof_windows = 0; b->prof_bytes[0] = b->prof_bytes[1] = 0.0;
+    b->panel = panel; b->p_paths = nullptr; b->p_pcap = 0; b->pinfo_nt = b->pinfo_c = 0;
     b->nb = (int)(((size_t)(b->N + 1) * (b->W > 8 ? b->W : 8) + 255) / 256);   // >= blocks of k_marg<.., true>
     hipError_t e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc((void **)&b->d_wd, sizeof(win_desc) * n);
+    if (e == hipSuccess) e = hipMalloc((void **)&b->d_wd, sizeof(win_desc) * n * (panel ? 2 : 1));
     if (e == hipSuccess) e = hipMalloc((void **)&b->d_states, sizeof(dev_state) * n);
     if (e == hipSuccess) e = hipMalloc((void **)&b->d_partial, sizeof(double) * (size_t)b->nb * n);
     if (e != hipSuccess) { gh_batch_destroy(b); return fail(GH_ERR_NOMEM, "batch allocation failed: %s", hipGetErrorString(e)); }
     *out = b;
     return GH_OK;
 }
+extern "C" int gh_batch_create(gh_t **handles, int n, gh_batch_t **out) { return batch_create(handles, n, out, false); }
+extern "C" int gh_panel_create(gh_t **handles, int n, gh_batch_t **out) { return batch_create(handles, n, out, true); }
 
 // gh_batch_spin's bookkeeping over all windows in one launch each: the control words a spin starts from (k_spin_reset's), and
 // every window's state into one array the host fetches with one copy (256 small copies cost 4 ms)
@@ -2528,23 +2543,15 @@ static bool pipe_instantiated(int L, int nt)
 // the window pipeline over the windows `wd` describes: marginals, snapshot and the full table for every window (what the batched
 // launches do in front of their first path), then ONE launch that carries every window through all its paths (wpipe.hpp)
 // launch_only: the preamble has run (batch_pipe_preamble) and b->d_wd + d_off holds the n descriptors this launch takes
-static int batch_run_pipe(gh_batch *b, const std::vector<win_desc> &wd, int max_paths, double min_remove, int nt, bool launch_only = false, int d_off = 0, bool no_sync = false)
+// the pipeline's preamble over the n windows whose descriptors stand at gwd, on `st`: marginals, snapshot and the full table of every
+// window.  N, W: the largest window's -- they size the grids; every kernel takes its window's own shape from the descriptor
+static void pipe_preamble(const gh_handle *h0, hipStream_t st, const win_desc *gwd, int n, int N, int W, int L)
 {
-    const int n = (int)wd.size();
-    if (n == 0) return GH_OK;
-    if (!launch_only) HIPCHK(hipMemcpyAsync(b->d_wd, wd.data(), sizeof(win_desc) * n, hipMemcpyHostToDevice, b->stream));
-    gh_handle *h0 = b->hs[0];
     const bool f64 = h0->cfg.storage == GH_STORAGE_F64;
-    const int N = b->N, W = b->W, L = b->L;
     const int bwm = h0->wmode == WM_SEG ? WM_SPEC : h0->wmode;
     const unsigned marg_gx = (unsigned)(((N + 1) * 8 + 255) / 256);
     size_t lt_nb = ((size_t)(N + LT_PAD) * L * LT_BLK + 255) / 256;
     if (lt_nb > 4096) lt_nb = 4096;
-    hipStream_t st = b->stream;
-    const win_desc *gwd = b->d_wd + d_off;
-    if (!launch_only) {
-    hipLaunchKernelGGL(k_batch_reset, dim3(n), dim3(64), 0, b->stream, (const win_desc *)b->d_wd);
-    HIPCHK(hipStreamSynchronize(b->stream));        // wd is a host temporary
     hipLaunchKernelGGL(k_rearm, dim3(n), dim3(64), 0, st, (dev_state *)nullptr, gwd, 0);
     if (f64) {
         hipLaunchKernelGGL((k_marg<double, false>), dim3(marg_gx, n), dim3(256), 0, st, (double *)nullptr, N, W,
@@ -2568,16 +2575,45 @@ static int batch_run_pipe(gh_batch *b, const std::vector<win_desc> &wd, int max_
                            (const uint32_t *)nullptr, (const double *)nullptr, (double *)nullptr, (dev_state *)nullptr,
                            (const uint8_t *)nullptr, gwd, 0, walk_depth2_ok(bwm, L), (double *)nullptr, (double *)nullptr, h0->sm, (const float *)nullptr);
     }
-    HIPCHK(hipGetLastError());
-    if (nt == 0) return GH_OK;                      // (the preamble only: batch_pipe_preamble)
-    }
+}
+// the pipeline's launch parameters for windows of up to N SNPs (C and the LDS: sized by the largest window) and their LDS bytes
+static pipe_params pipe_make_params(const gh_handle *h0, int N, int W, int L, int nt, bool wide, int max_paths, double min_remove, size_t *lds)
+{
+    const bool f64 = h0->cfg.storage == GH_STORAGE_F64;
     const int nr = pipe_sweep_threads(nt);
     pipe_params P;
     P.N = N; P.W = W; P.L = L; P.mt = h0->cfg.marginal_term ? 1 : 0; P.col = (h0->cfg.cond_mode == GH_COND_C || h0->cfg.cond_mode == GH_COND_E) ? 1 : 0;
-    P.C = pipe_chunk(N, L, nr, f64 ? 8 : 4, P.mt); P.max_paths = max_paths; P.cond_mode = h0->cfg.cond_mode;
+    P.C = wide ? pipe_chunk_w(N, L, nr, f64 ? 8 : 4, P.mt) : pipe_chunk(N, L, nr, f64 ? 8 : 4, P.mt);
+    P.max_paths = max_paths; P.cond_mode = h0->cfg.cond_mode;
     P.synth = getenv("GH_PIPE_SYNTH") ? (atoi(getenv("GH_PIPE_SYNTH")) != 0) : 1;          // (wpipe.hpp, the loaders: what it gains and costs)
-    P.offer_zero = h0->cfg.offer_zero; P.prof = (b->prof_every > 0 || getenv("GH_PIPE_STAMPS")) ? 1 : 0; P.min_remove = min_remove; P.sm = h0->sm;
-    const size_t lds = pipe_lds_bytes(N, L, P.C, nr, f64 ? 8 : 4, P.mt);
+    P.offer_zero = h0->cfg.offer_zero; P.prof = 0; P.min_remove = min_remove; P.sm = h0->sm;
+    *lds = wide ? pipe_lds_bytes_w(N, L, P.C, nr, f64 ? 8 : 4, P.mt) : pipe_lds_bytes(N, L, P.C, nr, f64 ? 8 : 4, P.mt);
+    return P;
+}
+
+// the window pipeline over the windows `wd` describes: marginals, snapshot and the full table for every window (what the batched
+// launches do in front of their first path), then ONE launch that carries every window through all its paths (wpipe.hpp)
+// launch_only: the preamble has run (batch_pipe_preamble) and b->d_wd + d_off holds the n descriptors this launch takes
+static int batch_run_pipe(gh_batch *b, const std::vector<win_desc> &wd, int max_paths, double min_remove, int nt, bool launch_only = false, int d_off = 0, bool no_sync = false)
+{
+    const int n = (int)wd.size();
+    if (n == 0) return GH_OK;
+    if (!launch_only) HIPCHK(hipMemcpyAsync(b->d_wd, wd.data(), sizeof(win_desc) * n, hipMemcpyHostToDevice, b->stream));
+    gh_handle *h0 = b->hs[0];
+    const bool f64 = h0->cfg.storage == GH_STORAGE_F64;
+    const int N = b->N, W = b->W, L = b->L;
+    hipStream_t st = b->stream;
+    const win_desc *gwd = b->d_wd + d_off;
+    if (!launch_only) {
+    hipLaunchKernelGGL(k_batch_reset, dim3(n), dim3(64), 0, b->stream, (const win_desc *)b->d_wd);
+    HIPCHK(hipStreamSynchronize(b->stream));        // wd is a host temporary
+    pipe_preamble(h0, st, gwd, n, N, W, L);
+    HIPCHK(hipGetLastError());
+    if (nt == 0) return GH_OK;                      // (the preamble only: batch_pipe_preamble)
+    }
+    size_t lds = 0;
+    pipe_params P = pipe_make_params(h0, N, W, L, nt, false, max_paths, min_remove, &lds);
+    P.prof = (b->prof_every > 0 || getenv("GH_PIPE_STAMPS")) ? 1 : 0;
     b->pused[0] = b->pused[1] = 0;
     auto pmark = [&](hipStream_t s_) {
         if (b->pused[0] >= b->pev[0].size()) {
@@ -2739,13 +2775,8 @@ static int batch_run_pipe_wide(gh_batch *b, const std::vector<win_desc> &wd, int
     const int N = b->N, W = b->W, L = b->L;
     const bool own = d_off < 0;                     // (else: the descriptors stand at b->d_wd + d_off, the caller waits for `stream`)
     if (own) { stream = b->stream; d_off = 0; HIPCHK(hipMemcpyAsync(b->d_wd, wd.data(), sizeof(win_desc) * n, hipMemcpyHostToDevice, b->stream)); }
-    const int nr = pipe_sweep_threads(nt);
-    pipe_params P;
-    P.N = N; P.W = W; P.L = L; P.mt = h0->cfg.marginal_term ? 1 : 0; P.col = (h0->cfg.cond_mode == GH_COND_C || h0->cfg.cond_mode == GH_COND_E) ? 1 : 0;
-    P.C = pipe_chunk_w(N, L, nr, f64 ? 8 : 4, P.mt); P.max_paths = max_paths; P.cond_mode = h0->cfg.cond_mode;
-    P.synth = getenv("GH_PIPE_SYNTH") ? (atoi(getenv("GH_PIPE_SYNTH")) != 0) : 1;
-    P.offer_zero = h0->cfg.offer_zero; P.prof = 0; P.min_remove = min_remove; P.sm = h0->sm;
-    const size_t lds = pipe_lds_bytes_w(N, L, P.C, nr, f64 ? 8 : 4, P.mt);
+    size_t lds = 0;
+    const pipe_params P = pipe_make_params(h0, N, W, L, nt, true, max_paths, min_remove, &lds);
     const hipError_t le = f64 ? launch_wpipe_w<double>(L, nt, P, b->d_wd + d_off, n, lds, stream) : launch_wpipe_w<float>(L, nt, P, b->d_wd + d_off, n, lds, stream);
     if (le != hipSuccess) return fail(GH_ERR_HIP, "gh_batch_spin: the wide pipeline launch failed (L=%d, %d threads, %zu bytes of LDS): %s", L, nt, lds, hipGetErrorString(le));
     if (own) HIPCHK(hipStreamSynchronize(b->stream));        // wd is a host temporary
@@ -2754,12 +2785,12 @@ static int batch_run_pipe_wide(gh_batch *b, const std::vector<win_desc> &wd, int
 
 // gh_spin over some windows of a batch from a few host threads, every window on its own stream (the windows' kernel chains
 // interleave on the GPU).  A job is (window, paths it already has): the spin writes the window's remaining paths behind them.
+// paths_off (panels): window w's paths stand at paths_out + paths_off[w], [max_paths][N_w + 1]; nullptr: [n][max_paths][N + 1]
 static int batch_spin_on_streams(gh_batch *b, const std::vector<std::pair<int, int>> &jobs, int max_paths, double min_remove,
-                                 uint8_t *paths_out, gh_path_rec *recs, int *n_out, int *hole_at)
+                                 uint8_t *paths_out, gh_path_rec *recs, int *n_out, int *hole_at, const int64_t *paths_off = nullptr)
 {
     const int nj = (int)jobs.size();
     if (nj == 0) return GH_OK;
-    const size_t n1 = (size_t)b->N + 1;
     static const int nthr_env = getenv("GH_BATCH_THREADS") ? atoi(getenv("GH_BATCH_THREADS")) : 8;
     const int nthr = nthr_env < 1 ? 1 : (nthr_env > nj ? nj : nthr_env);
     std::vector<int> rcs(nj, GH_OK);
@@ -2773,7 +2804,9 @@ static int batch_spin_on_streams(gh_batch *b, const std::vector<std::pair<int, i
             const int w = jobs[q].first, nd = jobs[q].second;
             int n2 = 0, hole2 = 0;
             if (nd < max_paths) {
-                rcs[q] = gh_spin(b->hs[w], max_paths - nd, min_remove, paths_out + n1 * ((size_t)max_paths * w + nd), recs + (size_t)max_paths * w + nd, &n2, &hole2);
+                const size_t n1 = (size_t)b->hs[w]->N + 1;
+                uint8_t *pw = paths_off ? paths_out + paths_off[w] + n1 * nd : paths_out + n1 * ((size_t)max_paths * w + nd);
+                rcs[q] = gh_spin(b->hs[w], max_paths - nd, min_remove, pw, recs + (size_t)max_paths * w + nd, &n2, &hole2);
                 if (rcs[q]) errs[q] = gh_last_error();
             }
             n_out[w] = nd + n2;
@@ -2793,6 +2826,7 @@ extern "C" int gh_batch_spin(gh_batch_t *b, int max_paths, double min_remove, ui
                              gh_path_rec *recs, int *n_out, int *hole_at)
 {
     if (!b || !paths_out || !recs || !n_out || !hole_at || max_paths < 1) return fail(GH_ERR_ARG, "bad argument");
+    if (b->panel) return fail(GH_ERR_ARG, "gh_batch_spin: this is a panel (gh_panel_create): spin it with gh_panel_spin");
     HIPCHK(hipSetDevice(b->dev));
     const bool hprof = getenv("GH_PIPE_STAMPS") != nullptr;        // host phases of this call on stderr
     auto tnow = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -2888,6 +2922,7 @@ extern "C" int gh_batch_spin(gh_batch_t *b, int max_paths, double min_remove, ui
         wd[w].tband = h->tband;
         wd[w].gw = h->pipe_gw;
         wd[w].wdir = h->pipe_gw ? reinterpret_cast<int *>(h->pipe_gw + (size_t)PIPE_WMAX * pipe_wrec_doubles(b->L)) : nullptr;
+        wd[w].N = h->N; wd[w].W = h->W;
         h->have_orig = true;
     }
     std::vector<dev_state> hs(n);
@@ -3022,6 +3057,243 @@ extern "C" int gh_batch_spin(gh_batch_t *b, int max_paths, double min_remove, ui
     return GH_OK;
 }
 
+// ---- panels: windows of differing N, W and L (gh_panel_*) ----------------------------------------------------------------------
+// The windows go in one GROUP per lag count L (the pipeline is instantiated per lag count).  A group the pipeline can carry -- the
+// eligibility test gh_batch_spin makes, over the group's own windows -- runs the pipeline's preamble and launches, sized by its
+// largest window, on one of the batch's four streams; every kernel takes its window's own N and W from the descriptor.  What no
+// group carries (a group too small, a lag count beyond the pipeline, a hole, too many five-candidate positions, the remaining paths
+// of an aborted window) is finished by gh_spin window by window on its own stream, as in gh_batch_spin.
+extern "C" int gh_panel_spin(gh_batch_t *b, int max_paths, double min_remove, uint8_t *paths_out, const int64_t *paths_off,
+                             gh_path_rec *recs, int *n_out, int *hole_at)
+{
+    if (!b || !paths_out || !paths_off || !recs || !n_out || !hole_at || max_paths < 1) return fail(GH_ERR_ARG, "bad argument");
+    if (!b->panel) return fail(GH_ERR_ARG, "gh_panel_spin: not a panel (gh_panel_create)");
+    HIPCHK(hipSetDevice(b->dev));
+    const int n = b->n;
+    int rc;
+    for (int w = 0; w < n; w++) {
+        if (paths_off[w] < 0) return fail(GH_ERR_ARG, "gh_panel_spin: window %d has a negative path offset", w);
+        if ((rc = alloc_lt(b->hs[w]))) return rc;
+    }
+    for (int w = 0; w < n; w++) HIPCHK(hipStreamSynchronize(b->hs[w]->stream));     // (the handles' fills: see gh_batch_spin)
+    gh_handle *h0 = b->hs[0];
+    const bool f64 = h0->cfg.storage == GH_STORAGE_F64;
+    const int es = f64 ? 8 : 4, mt = h0->cfg.marginal_term ? 1 : 0;
+    const int pipe_env = getenv("GH_PIPE") ? atoi(getenv("GH_PIPE")) : 1;
+    const int pipe_min = getenv("GH_PIPE_MIN") ? atoi(getenv("GH_PIPE_MIN")) : 24;
+    const bool wide_env = !(getenv("GH_PIPE_WIDE") && atoi(getenv("GH_PIPE_WIDE")) == 0);
+    const int bwm0 = h0->wmode == WM_SEG ? WM_SPEC : h0->wmode;
+    struct pgroup { int L, nt, N, W; std::vector<int> ws; };
+    std::vector<pgroup> groups;
+    std::vector<std::pair<int, int>> later;     // (window, paths done): gh_spin finishes them
+    {
+        std::map<int, std::vector<int>> byL;
+        for (int w = 0; w < n; w++) byL[b->hs[w]->L].push_back(w);
+        for (auto &kv : byL) {
+            pgroup g;
+            g.L = kv.first; g.nt = pipe_threads(g.L); g.N = 0; g.W = 0;
+            const bool ok = pipe_env && g.nt && pipe_instantiated(g.L, g.nt) && walk_depth2_ok(bwm0, g.L);
+            for (int w : kv.second) {
+                const gh_handle *h = b->hs[w];
+                if (ok && pipe_spec_ok(h) && (unsigned long long)(h->N + 2) * 49ull * (unsigned long long)h->W < (1ull << 31)) {   // (the sweep's 32-bit element offsets)
+                    g.ws.push_back(w);
+                    if (h->N > g.N) g.N = h->N;
+                    if (h->W > g.W) g.W = h->W;
+                } else later.emplace_back(w, 0);
+            }
+            if (!g.ws.empty() && (int)g.ws.size() >= pipe_min && pipe_chunk(g.N, g.L, pipe_sweep_threads(g.nt), es, mt) > 0) groups.push_back(g);
+            else for (int w : g.ws) later.emplace_back(w, 0);
+        }
+    }
+    std::vector<int> grp(n, -1);
+    for (size_t gi = 0; gi < groups.size(); gi++)
+        for (int w : groups[gi].ws) grp[w] = (int)gi;
+    // the pipeline's paths, [window][max_paths][N_w + 1] in window order; its records as gh_batch_spin's, [n][max_paths]
+    std::vector<size_t> doff(n, 0);
+    size_t ptot = 0;
+    for (int w = 0; w < n; w++)
+        if (grp[w] >= 0) { doff[w] = ptot; ptot += ((size_t)b->hs[w]->N + 1) * max_paths; }
+    b->pipe_windows = b->pipe_aborted = 0;
+    b->pinfo_nt = b->pinfo_c = 0;
+    b->pused[0] = b->pused[1] = 0;
+    std::vector<dev_state> hs(n);
+    if (!groups.empty()) {
+        if (ptot > b->p_pcap) {
+            HIPCHK(hipStreamSynchronize(b->stream));
+            hipFree(b->p_paths); b->p_paths = nullptr; b->p_pcap = 0;
+            HIPCHK(hipMalloc((void **)&b->p_paths, ptot));
+            b->p_pcap = ptot;
+        }
+        if (max_paths > b->cap_paths) {
+            HIPCHK(hipStreamSynchronize(b->stream));
+            hipFree(b->d_recs); b->d_recs = nullptr; b->cap_paths = 0;
+            HIPCHK(hipMalloc((void **)&b->d_recs, sizeof(gh_path_rec) * (size_t)max_paths * n));
+            b->cap_paths = max_paths;
+        }
+        for (int g = 0; g < 3; g++)
+            if (!b->gstream[g]) HIPCHK(hipStreamCreateWithFlags(&b->gstream[g], hipStreamNonBlocking));
+        const hipStream_t streams[4] = {b->stream, b->gstream[0], b->gstream[1], b->gstream[2]};
+        // per-window buffers of the pipeline (gh_batch_spin's, at the window's own N and L)
+        for (int w = 0; w < n; w++) {
+            if (grp[w] < 0) continue;
+            gh_handle *h = b->hs[w];
+            if (!h->pipe_pk) HIPCHK(hipMalloc((void **)&h->pipe_pk, sizeof(unsigned long long) * ((size_t)h->N + 2)));
+            const size_t need = sizeof(double) * ((size_t)h->N + LT_PAD) * 16 * (size_t)h->L;
+            if (h->pipe_gp_bytes < need) {
+                hipFree(h->pipe_gp); h->pipe_gp = nullptr; h->pipe_gp_bytes = 0;
+                HIPCHK(hipMalloc((void **)&h->pipe_gp, need));
+                h->pipe_gp_bytes = need;
+            }
+            if (h->cfg.marginal_term && !h->pipe_lm) HIPCHK(hipMalloc((void **)&h->pipe_lm, sizeof(double) * 4 * ((size_t)h->N + 2)));
+            if (h->cfg.cond_mode == GH_COND_C || h->cfg.cond_mode == GH_COND_E) {
+                const size_t nel = h->n_cells * CELL;
+                if (!h->tband && hipMalloc(&h->tband, nel * esize(h)) != hipSuccess) { h->tband = nullptr; return fail(GH_ERR_NOMEM, "hipMalloc for the to-major band failed"); }
+                if (h->tband_epoch != h->band_epoch) {
+                    const unsigned nbt = (unsigned)((nel + 255) / 256);
+                    if (f64) hipLaunchKernelGGL(k_band_to_major<double>, dim3(nbt), dim3(256), 0, b->stream, (const double *)h->band, (double *)h->tband, nel, h->W);
+                    else hipLaunchKernelGGL(k_band_to_major<float>, dim3(nbt), dim3(256), 0, b->stream, (const float *)h->band, (float *)h->tband, nel, h->W);
+                    h->tband_epoch = h->band_epoch;
+                }
+            }
+        }
+        // every pipeline window's descriptor, group by group (d_wd[0 .. np)); ord[i] = the window of descriptor i
+        std::vector<win_desc> wd(n);
+        std::vector<int> ord, gfirst;
+        for (const pgroup &g : groups) {
+            gfirst.push_back((int)ord.size());
+            for (int w : g.ws) {
+                gh_handle *h = b->hs[w];
+                win_desc &d = wd[w];
+                memset(&d, 0, sizeof(d));
+                d.band = h->band; d.cnt = h->cnt; d.marg = h->marg; d.minfo = h->minfo; d.nvalid = h->nvalid; d.cmask = h->cmask;
+                d.rinfo = h->need_rinfo ? h->rinfo : nullptr; d.G = h->lt; d.Ht = nullptr; d.Yt = nullptr; d.st = h->dstate;
+                d.partial = b->d_partial + (size_t)w * b->nb;
+                d.paths = b->p_paths + doff[w];
+                d.recs = b->d_recs + (size_t)max_paths * w;
+                d.snap = h->have_orig ? 0 : 1;
+                d.pk = h->pipe_pk; d.gp = h->pipe_gp; d.lmr = h->pipe_lm; d.tband = h->tband; d.gw = h->pipe_gw;
+                d.wdir = h->pipe_gw ? reinterpret_cast<int *>(h->pipe_gw + (size_t)PIPE_WMAX * pipe_wrec_doubles(h->L)) : nullptr;
+                d.N = h->N; d.W = h->W;
+                h->have_orig = true;
+                ord.push_back(w);
+            }
+        }
+        const int np = (int)ord.size();
+        std::vector<win_desc> all(np);
+        for (int i = 0; i < np; i++) all[i] = wd[ord[i]];
+        {
+            HIPCHK(hipMemcpyAsync(b->d_wd, all.data(), sizeof(win_desc) * np, hipMemcpyHostToDevice, b->stream));
+            hipLaunchKernelGGL(k_batch_reset, dim3(np), dim3(64), 0, b->stream, (const win_desc *)b->d_wd);
+            HIPCHK(hipStreamSynchronize(b->stream));
+            // the preambles, group g on stream g % 4 (sized by the group's largest window)
+            for (size_t gi = 0; gi < groups.size(); gi++) {
+                const pgroup &g = groups[gi];
+                pipe_preamble(h0, streams[gi % 4], b->d_wd + gfirst[gi], (int)g.ws.size(), g.N, g.W, g.L);
+            }
+            HIPCHK(hipGetLastError());
+            for (int s = 0; s < 4; s++) HIPCHK(hipStreamSynchronize(streams[s]));
+        }
+        {
+            std::vector<dev_state> tmp(np);
+            HIPCHK(hipMemcpyAsync(b->d_wd, all.data(), sizeof(win_desc) * np, hipMemcpyHostToDevice, b->stream));
+            hipLaunchKernelGGL(k_batch_states, dim3(np), dim3(64), 0, b->stream, (const win_desc *)b->d_wd, b->d_states);
+            HIPCHK(hipMemcpyAsync(tmp.data(), b->d_states, sizeof(dev_state) * np, hipMemcpyDeviceToHost, b->stream));
+            HIPCHK(hipStreamSynchronize(b->stream));
+            for (int i = 0; i < np; i++) hs[ord[i]] = tmp[i];
+        }
+        // the launches: per group the narrow one over its ranked windows and the WIDE one over those with five-candidate
+        // positions; their descriptor lists at d_wd[n ..], launch k on stream k % 4
+        struct plaunch { int gi; bool wide; int off, cnt; };
+        std::vector<plaunch> launches;
+        std::vector<win_desc> lists;
+        std::vector<char> listed(n, 0);
+        for (size_t gi = 0; gi < groups.size(); gi++) {
+            const pgroup &g = groups[gi];
+            const bool wide_on = wide_env && pipe_wide_instantiated(g.L, g.nt) && !h0->cfg.offer_zero &&
+                                 pipe_chunk_w(g.N, g.L, pipe_sweep_threads(g.nt), es, mt) > 0;
+            std::vector<win_desc> nar, wid;
+            for (int w : g.ws) {
+                const bool live = !hs[w].stop && hs[w].first_hole > b->hs[w]->N;
+                if (live && hs[w].ranked != 0 && hs[w].narrow != 0) { nar.push_back(wd[w]); listed[w] = 1; }
+                else if (live && hs[w].ranked == 0 && wide_on && b->hs[w]->N < 65536) {
+                    gh_handle *h = b->hs[w];
+                    const size_t need = pipe_gw_bytes(h->N, h->L);
+                    if (h->pipe_gw_bytes < need) {
+                        hipFree(h->pipe_gw); h->pipe_gw = nullptr; h->pipe_gw_bytes = 0;
+                        HIPCHK(hipMalloc((void **)&h->pipe_gw, need));
+                        h->pipe_gw_bytes = need;
+                    }
+                    wd[w].gw = h->pipe_gw;
+                    wd[w].wdir = reinterpret_cast<int *>(h->pipe_gw + (size_t)PIPE_WMAX * pipe_wrec_doubles(h->L));
+                    wid.push_back(wd[w]);
+                    listed[w] = 1;
+                }
+            }
+            if (!nar.empty()) { launches.push_back({(int)gi, false, n + (int)lists.size(), (int)nar.size()}); lists.insert(lists.end(), nar.begin(), nar.end()); }
+            if (!wid.empty()) { launches.push_back({(int)gi, true, n + (int)lists.size(), (int)wid.size()}); lists.insert(lists.end(), wid.begin(), wid.end()); }
+        }
+        if (!lists.empty()) HIPCHK(hipMemcpyAsync(b->d_wd + n, lists.data(), sizeof(win_desc) * lists.size(), hipMemcpyHostToDevice, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+        int most = 0;
+        for (size_t k = 0; k < launches.size(); k++) {
+            const plaunch &q = launches[k];
+            const pgroup &g = groups[q.gi];
+            const hipStream_t st = streams[k % 4];
+            size_t lds = 0;
+            const pipe_params P = pipe_make_params(h0, g.N, g.W, g.L, g.nt, q.wide, max_paths, min_remove, &lds);
+            const win_desc *gwd = b->d_wd + q.off;
+            hipError_t le;
+            if (q.wide) le = f64 ? launch_wpipe_w<double>(g.L, g.nt, P, gwd, q.cnt, lds, st) : launch_wpipe_w<float>(g.L, g.nt, P, gwd, q.cnt, lds, st);
+            else le = f64 ? launch_wpipe<double>(g.L, g.nt, P, gwd, q.cnt, lds, st) : launch_wpipe<float>(g.L, g.nt, P, gwd, q.cnt, lds, st);
+            if (le != hipSuccess)
+                return fail(GH_ERR_HIP, "gh_panel_spin: the %s pipeline launch failed (L=%d, %d threads, %zu bytes of LDS): %s", q.wide ? "wide" : "narrow",
+                            g.L, g.nt, lds, hipGetErrorString(le));
+            if (!q.wide && q.cnt > most) { most = q.cnt; b->pinfo_nt = g.nt; b->pinfo_c = P.C; }
+        }
+        for (int s = 0; s < 4; s++) HIPCHK(hipStreamSynchronize(streams[s]));
+        {
+            std::vector<dev_state> tmp(np);
+            hipLaunchKernelGGL(k_batch_states, dim3(np), dim3(64), 0, b->stream, (const win_desc *)b->d_wd, b->d_states);
+            HIPCHK(hipMemcpyAsync(tmp.data(), b->d_states, sizeof(dev_state) * np, hipMemcpyDeviceToHost, b->stream));
+            HIPCHK(hipStreamSynchronize(b->stream));
+            for (int i = 0; i < np; i++) hs[ord[i]] = tmp[i];
+        }
+        for (int w = 0; w < n; w++) {
+            if (grp[w] < 0) continue;
+            if (!listed[w]) hs[w].pipe_status = PIPE_NOT_STARTED;
+            if (hs[w].pipe_status == PIPE_NOT_STARTED) later.emplace_back(w, 0);
+            else if (hs[w].pipe_status == PIPE_ABORTED) { later.emplace_back(w, hs[w].n_done); b->pipe_aborted++; b->pipe_windows++; }
+            else if (hs[w].pipe_status == PIPE_DONE) b->pipe_windows++;
+            else return fail(GH_ERR_STATE, "gh_panel_spin: window %d left the pipeline in state %d", w, hs[w].pipe_status);
+        }
+        // the pipeline's paths and records to the caller, in runs of windows that lie back to back on both sides
+        for (int w = 0; w < n;) {
+            if (grp[w] < 0) { w++; continue; }
+            int e = w + 1;
+            while (e < n && grp[e] >= 0 && paths_off[e] - paths_off[w] == (int64_t)(doff[e] - doff[w])) e++;
+            const size_t bytes = doff[e - 1] + ((size_t)b->hs[e - 1]->N + 1) * max_paths - doff[w];
+            HIPCHK(hipMemcpyAsync(paths_out + paths_off[w], b->p_paths + doff[w], bytes, hipMemcpyDeviceToHost, b->stream));
+            HIPCHK(hipMemcpyAsync(recs + (size_t)max_paths * w, b->d_recs + (size_t)max_paths * w, sizeof(gh_path_rec) * (size_t)max_paths * (e - w),
+                                  hipMemcpyDeviceToHost, b->stream));
+            w = e;
+        }
+        HIPCHK(hipStreamSynchronize(b->stream));
+        for (int w = 0; w < n; w++) {
+            if (grp[w] < 0) continue;
+            gh_handle *h = b->hs[w];
+            n_out[w] = hs[w].n_done;
+            hole_at[w] = hs[w].stop ? hs[w].hole_at : 0;
+            const bool kept = h->tband && h->tband_epoch == h->band_epoch &&
+                              (hs[w].pipe_status == PIPE_DONE || hs[w].pipe_status == PIPE_ABORTED) &&
+                              (h->cfg.cond_mode == GH_COND_C || h->cfg.cond_mode == GH_COND_E);
+            h->dirty_marg = h->dirty_lt = true; h->band_epoch++;
+            if (kept) h->tband_epoch = h->band_epoch;       // (the pipeline's sweep wrote both)
+            h->lt_inc_path = nullptr;
+        }
+    }
+    return batch_spin_on_streams(b, later, max_paths, min_remove, paths_out, recs, n_out, hole_at, paths_off);
+}
+
 extern "C" int gh_host_alloc(size_t bytes, void **out)
 {
     if (!out || bytes == 0) return fail(GH_ERR_ARG, "bad argument");
@@ -3039,8 +3311,13 @@ extern "C" int gh_host_free(void *p)
 extern "C" int gh_batch_pipe_info(gh_batch_t *b, int32_t out[4])
 {
     if (!b || !out) return fail(GH_ERR_ARG, "bad argument");
-    const int nt = pipe_threads(b->L);
     out[0] = b->pipe_windows; out[1] = b->pipe_aborted;
+    if (b->panel) {
+        out[2] = b->pipe_windows ? b->pinfo_nt : 0;
+        out[3] = b->pipe_windows ? b->pinfo_c : 0;
+        return GH_OK;
+    }
+    const int nt = pipe_threads(b->L);
     out[2] = b->pipe_windows ? nt : 0;
     out[3] = b->pipe_windows ? pipe_chunk(b->N, b->L, pipe_sweep_threads(nt), b->hs[0]->cfg.storage == GH_STORAGE_F64 ? 8 : 4, b->hs[0]->cfg.marginal_term) : 0;
     return GH_OK;

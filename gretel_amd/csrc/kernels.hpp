@@ -119,6 +119,8 @@ struct win_desc {
     void *tband;            // k_wpipe under the column conditionals: the to-major copy of the band (kept in step)
     double *gw;             // k_wpipe<.., WIDE>: the side table of the window's five-candidate positions (wpipe.hpp: PIPE_WMAX records)
     int *wdir;              // ... and, per chunk, the records the chunk can see: first | count << 16
+    int N, W;               // this window's SNP count and band (a panel's windows differ; gh_batch_spin: the batch's own).  The
+                            // preamble (k_marg<T, false>, k_snapshot, k_lt) and k_wpipe take them from here, not from their arguments
 };
 
 // Band layout: band[i][a][d-1][b] -- position, FROM-symbol, distance, to-symbol.  Everything a path touches at position i
@@ -745,6 +747,12 @@ k_marg(T *band, int N, int W, double *cnt, double *marg,
     }
     if (wd) {
         const win_desc &d = wd[blockIdx.y];
+        if (!RW) {
+            // the preamble of the window pipeline: this window's shape (a panel's grid is sized by its largest window).  (The
+            // fused reweight of the batched launches keeps the batch-wide N and W: they only run over windows of one shape.)
+            N = d.N; W = d.W;
+            if ((int)(blockIdx.x * (blockDim.x >> 3)) > N) return;
+        }
         band = (T *)d.band; cnt = d.cnt; marg = d.marg; nvalid = d.nvalid; cmask = d.cmask; minfo = d.minfo; st = d.st; rinfo = d.rinfo;
         if (RW) { rw_path = d.paths + (size_t)spin * (N + 1); partial = d.partial; if (G) G = d.G; }
         live = !st->stop;
@@ -981,6 +989,7 @@ __global__ void k_snapshot(double *dst_minfo, const double *src_minfo, int N, co
 {
     if (wd) {
         if (!wd[blockIdx.y].snap) return;
+        N = wd[blockIdx.y].N;
         dst_minfo = wd[blockIdx.y].minfo;
         src_minfo = dst_minfo;
     }
@@ -1084,6 +1093,9 @@ k_lt(const T *band, int N, int W, int L, int cond_mode, int marginal_term /* = b
 {
     if (wd) {
         const win_desc &d = wd[blockIdx.y];
+        N = d.N; W = d.W;
+        // (a panel's grid is sized by its largest window: a block with nothing of this window's table leaves)
+        if (!inc_path && (size_t)blockIdx.x * blockDim.x >= (size_t)(N + LT_PAD) * 6 * L * LT_ROW) return;
         band = (const T *)d.band; cnt = d.cnt; nvalid = d.nvalid; cmask = d.cmask; minfo = d.minfo; G = d.G; st = d.st;
         Ht = d.Ht; Yt = d.Yt;
         if (st->stop) return;

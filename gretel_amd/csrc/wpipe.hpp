@@ -1159,6 +1159,9 @@ __global__ void __launch_bounds__(NT, (NT == 512 && LC <= 6) ? 4 : (NT == 1024 ?
     const int RS = XD + DL::YPOS;
     extern __shared__ __align__(16) double smem[];
     const win_desc d = wd[blockIdx.x];
+    // this window's shape (a panel's windows differ in N and W; C and the LDS were sized by the largest N): every role below reads
+    // P.N / P.W, and N -- hence the chunk and epoch counts every barrier loop runs -- is one value per workgroup
+    P.N = d.N; P.W = d.W;
     dev_state *st = d.st;
     const int N = P.N, C = P.C;
     const int npos = C + WALK_OV + (WIDE ? LC : 0);     // (WIDE: L more sources in front of the chunk -- pipe_wide_walker)

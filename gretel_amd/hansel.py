@@ -573,6 +573,65 @@ class HanselBatch:
         return out
 
 
+class HanselPanel(HanselBatch):
+    """Many windows of DIFFERING shape recovered together (gh_panel_*): one region (gene) per window, each with its own n_snps,
+    band and L.  The windows go in one group per L; the window pipeline (csrc/wpipe.hpp) carries every group it can, gh_spin
+    the rest.  Every window's results are those of its Hansel.spin alone.  The Hansels must already be filled and agree on
+    storage, modes and device."""
+
+    def __init__(self, hansels):
+        self.hansels = list(hansels)
+        if not self.hansels:
+            raise ValueError("empty panel")
+        for h in self.hansels:
+            h._ensure()
+        self._lib = self.hansels[0]._lib
+        arr = (C.c_void_p * len(self.hansels))(*[h._h for h in self.hansels])
+        b = C.c_void_p()
+        check(self._lib.gh_panel_create(arr, len(self.hansels), C.byref(b)))
+        self._b = b
+
+    def _host_buffers(self, n, max_paths, n1s):
+        """Page-locked result buffers as HanselBatch's: window w's paths are rows of n1s[w] bytes from self._hb_off[w]."""
+        key = (n, max_paths, tuple(n1s))
+        if getattr(self, "_hb_key", None) != key:
+            self._free_host_buffers()
+            off = np.zeros(n, dtype=np.int64)
+            if n > 1:
+                off[1:] = np.cumsum(np.asarray(n1s[:-1], dtype=np.int64) * max_paths)
+            sizes = (int(sum(n1s)) * max_paths, n * max_paths * 5 * 8)
+            blocks = [_PinnedBlock(self._lib, max(1, sz)) for sz in sizes]
+            self._hb_paths = blocks[0].array(np.uint8, sizes[0])
+            self._hb_recs = blocks[1].array(np.float64, sizes[1] // 8).reshape(n, max_paths, 5)
+            self._hb_off = off
+            self._hb_key = key
+        return self._hb_paths, self._hb_recs
+
+    def spin(self, max_paths=100, min_remove=0.01, copy=True):
+        """One dict per window, the keys and dtypes of Hansel.spin.  copy=False: views of the panel's page-locked buffers (see
+        HanselBatch.spin)."""
+        n = len(self.hansels)
+        n1s = [h.n + 1 for h in self.hansels]
+        paths, recs = self._host_buffers(n, max_paths, n1s)
+        off = self._hb_off
+        n_out = np.zeros(n, dtype=np.int32)
+        hole = np.zeros(n, dtype=np.int32)
+        check(self._lib.gh_panel_spin(self._b, int(max_paths), float(min_remove), _p(paths), _p(off), _p(recs), _p(n_out), _p(hole)))
+        out = []
+        for w in range(n):
+            k = int(n_out[w])
+            if k:
+                self.hansels[w].is_weighted = True
+            o = int(off[w])
+            pw = paths[o:o + max_paths * n1s[w]].reshape(max_paths, n1s[w])[:k]
+            rw = recs[w, :k]
+            if copy:
+                pw, rw = pw.copy(), rw.copy()
+            out.append(dict(n=k, hole_at=int(hole[w]), paths=pw, hp_current=rw[:, 0], hp_original=rw[:, 1], ratio=rw[:, 2],
+                            magnitude=rw[:, 3], min_marginal=rw[:, 4]))
+        return out
+
+
 class DeviceReads:
     """A support table resident in HBM (gh_reads_upload)."""
 

@@ -1,0 +1,111 @@
+"""
+`python -m gretel_amd.panel BAM VCF REGIONS -o OUT`: gretel over many regions (genes) of one BAM and VCF in one run.
+
+REGIONS is a BED file (contig, 0-based start, end, optional name: gretel_amd.util.read_regions).  The VCF is read once
+(util.process_vcf_regions), every region's Hansel is filled from the BAM in turn, and all of them are recovered together as one
+panel (hansel.HanselPanel: the window pipeline over the regions' differing shapes).  For each region the files
+
+    OUT/<name>/out.fasta, OUT/<name>/snp.fasta, OUT/<name>/gretel.crumbs
+
+are byte for byte what `python -m gretel_amd.cmd BAM VCF contig -s start -e end -o OUT/<name>` writes with the same options.
+A region gretel cannot recover (a SNP without pairwise evidence, or no read that carries two SNPs) gets gretel's [FAIL] text on
+stderr behind its name and is left out; the exit status is then 1, once every other region has been written.  Stdout: one line
+per recovered region -- name, SNPs, L, paths, distinct haplotypes.  The single-region debugging options (--debughpos,
+--debugreads, --debugpos, --dumpmatrix) are the single CLI's alone.
+"""
+from __future__ import annotations
+
+import argparse
+import io
+import os
+import sys
+
+from . import __version__
+from . import cmd
+from . import util
+from .hansel import HanselPanel
+
+
+def build_parser():
+    p = argparse.ArgumentParser(prog="gretel-panel", description="Gretel over many regions of one BAM / VCF, recovered as one panel.")
+    p.add_argument("bam")
+    p.add_argument("vcf")
+    p.add_argument("regions", help="BED file: contig, 0-based start, end, optional name (one region per line)")
+    p.add_argument("-o", "--out", default=".", help="output directory: one subdirectory per region name [default: .]")
+    p.add_argument("-p", "--paths", type=int, default=100, help="maximum number of paths to generate per region [default: 100]")
+    p.add_argument("--master", default=None, help="master FASTA used to fill the non-SNP positions (otherwise --gapchar)")
+    p.add_argument("--gapchar", default="N", help="character for non-SNP positions without --master [default: N]")
+    p.add_argument("--delchar", default="", help="character written for a deletion [default: nothing]")
+    p.add_argument("--max-depth", type=int, default=8000, help="read-buffer cap of the pileup, as in gretel_amd.cmd [default: 8000]")
+    p.add_argument("--pepper", action="store_true", help="permissive read filter (pysam stepper 'all' in the reference)")
+    p.add_argument("--version", action="version", version="%(prog)s " + __version__)
+    return p
+
+
+def _fail(name, text):
+    sys.stderr.write("%s: %s" % (name, text))
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    # everything that can be refused is refused before the first BAM read or GPU call
+    try:
+        regions = util.read_regions(args.regions)
+    except (OSError, ValueError) as e:
+        sys.stderr.write("[FAIL] %s\n" % e)
+        return 2
+    if not regions:
+        sys.stderr.write("[FAIL] %s holds no region\n" % args.regions)
+        return 2
+    if args.paths < 1:
+        sys.stderr.write("[FAIL] -p/--paths must be at least 1\n")
+        return 2
+    util.prefetch_bam(args.bam, regions[0]["contig"], regions[0]["start"], regions[0]["end"])
+    vcfs = util.process_vcf_regions(args.vcf, regions)
+    stepper = "all" if args.pepper else "samtools"
+    kept = []                   # (region, vcf_h, hansel)
+    failed = 0
+    for k, (r, vh) in enumerate(zip(regions, vcfs)):
+        hansel = None
+        if vh["N"] > 0:
+            try:
+                hansel = util.load_from_bam(args.bam, r["contig"], r["start"], r["end"], vh, max_depth=args.max_depth, stepper=stepper)
+            except ZeroDivisionError:           # no read carries two SNPs (gretel/util.py:333)
+                hansel = None
+        if k + 1 < len(regions):                # (the decoder reads the next region while this one is checked)
+            nx = regions[k + 1]
+            util.prefetch_bam(args.bam, nx["contig"], nx["start"], nx["end"])
+        if hansel is None:
+            pos = vh["snp_rev"][0] if vh["N"] > 0 else 0
+            _fail(r["name"], cmd.FAIL_TEXT % (1 if vh["N"] > 0 else 0, pos, 1 if vh["N"] > 0 else 0))
+            failed += 1
+            continue
+        hansel.snapshot_original()              # (as gretel_amd.cmd: cmd.py:79)
+        buf = io.StringIO()
+        if cmd.gap_report(hansel, vh, out=buf):
+            _fail(r["name"], buf.getvalue())
+            failed += 1
+            continue
+        kept.append((r, vh, hansel))
+    if kept:
+        results = HanselPanel([h for _, _, h in kept]).spin(args.paths, cmd.MIN_REMOVE)
+        with open(os.devnull, "w") as quiet:
+            for (r, vh, hansel), res in zip(kept, results):
+                paths = cmd.paths_of_spin(hansel, res, log=quiet)
+                dirn = os.path.join(args.out, r["name"])
+                os.makedirs(dirn, exist_ok=True)
+                ns = argparse.Namespace(out=dirn, master=args.master, start=r["start"], end=r["end"], gapchar=args.gapchar,
+                                        delchar=args.delchar)
+                cmd.write_outputs(paths, hansel, vh, ns)
+                sys.stdout.write("%s\t%d\t%d\t%d\t%d\n" % (r["name"], vh["N"], hansel.L, res["n"], len(paths)))
+    try:                        # (the decoder's kept working buffers: see gretel_amd.cmd)
+        from . import bamio
+        if getattr(bamio, "_io", None) is not None:
+            bamio.native_release_buffers()
+    except Exception:
+        pass
+    return 1 if failed else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -210,6 +210,17 @@ int gh_batch_pipe_info(gh_batch_t *b, int32_t out[4]);
 int gh_batch_profile_enable(gh_batch_t *b, int every);
 int gh_batch_profile_get(gh_batch_t *b, int kernel, double *total_ms, int64_t *launches, int32_t *windows, double *bytes_per_launch);
 
+/* Panels: a batch whose windows may differ in n_snps, band and L -- one region (gene) per window.  gh_panel_create makes the
+ * checks of gh_batch_create except for n_snps and band.  gh_panel_spin runs the windows in one group per L: every group the window
+ * pipeline can carry (as gh_batch_spin decides it, over the group's own windows) is carried by it, up to four groups at a time on
+ * the batch's streams; whatever it does not carry is finished by gh_spin window by window.  Each window's results are those of
+ * gh_spin on that window alone, bit for bit.  Window w's paths are [max_paths][N_w + 1] at paths_out + paths_off[w];
+ * recs: [n][max_paths], n_out / hole_at: [n] as in gh_batch_spin.  gh_batch_destroy, gh_batch_pipe_info (windows summed over the
+ * groups; threads and chunk of the largest launch) and gh_batch_profile_* take a panel; gh_batch_spin refuses one. */
+int gh_panel_create(gh_t **handles, int n, gh_batch_t **out);
+int gh_panel_spin(gh_batch_t *b, int max_paths, double min_remove, uint8_t *paths_out, const int64_t *paths_off,
+                  gh_path_rec *recs, int *n_out, int *hole_at);
+
 /* tensor export/import for --dumpmatrix (gretel/cmd.py:81-82) and tests:
  * band layout [(N+2)][band][7][7] as doubles; dense layout [7][7][N+2][N+2] (gretel/cmd.py:76-77). */
 int gh_export_band(gh_t *h, double *out);
