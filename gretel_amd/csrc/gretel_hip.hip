@@ -2372,22 +2372,20 @@ struct gh_batch {
     hipEvent_t gevent[3];
     win_desc *d_wd;
     dev_state *d_states;        // every window's dev_state, gathered by k_batch_states for one copy to the host
-    uint8_t *d_paths;
-    gh_path_rec *d_recs;
+    uint8_t *d_paths;           // window w's paths at d_paths + off[w], [max_paths][N_w + 1] back to back (batch_path_offsets)
+    gh_path_rec *d_recs;        // [n][max_paths]
     double *d_partial;
-    int cap_paths, nb;
+    int cap_paths, nb;          // cap_paths: the max_paths d_paths and d_recs hold
     int prof_every;             // gh_batch_profile_enable
-    int pipe_windows, pipe_aborted;     // last gh_batch_spin: windows the pipeline (wpipe.hpp) carried / handed back to gh_spin
+    int pipe_windows, pipe_aborted;     // the last spin: windows the pipeline (wpipe.hpp) carried / handed back to gh_spin
+    int pinfo_nt, pinfo_c;              // ... and threads and chunk of its group with the most windows
     std::vector<hipEvent_t> pev[2];     // [0] extension, [1] reweight: start/stop pairs of the last spin (group 0's stream)
     size_t pused[2];
     int prof_windows;
     double prof_bytes[2];
-    // panels (gh_panel_*): windows that differ in N, W and L.  N, W above are then the largest window's; d_wd holds 2n descriptors
-    // (every window's, and the lists the pipeline launches take); the pipeline's paths are [window][max_paths][N_w + 1] in p_paths
+    // d_wd holds 2n descriptors: every window's, and the lists the pipeline's launches take
+    // panels (gh_panel_*): windows that differ in N, W and L.  N, W above are then the largest window's
     bool panel;
-    uint8_t *p_paths;
-    size_t p_pcap;
-    int pinfo_nt, pinfo_c;      // the last gh_panel_spin: threads and chunk of the pipeline launch over the most windows
 };
 
 extern "C" int gh_batch_destroy(gh_batch_t *b)
@@ -2395,7 +2393,7 @@ extern "C" int gh_batch_destroy(gh_batch_t *b)
     if (!b) return GH_OK;
     hipSetDevice(b->dev);
     if (b->stream) hipStreamSynchronize(b->stream);
-    hipFree(b->d_wd); hipFree(b->d_states); hipFree(b->d_paths); hipFree(b->d_recs); hipFree(b->d_partial); hipFree(b->p_paths);
+    hipFree(b->d_wd); hipFree(b->d_states); hipFree(b->d_paths); hipFree(b->d_recs); hipFree(b->d_partial);
     for (int g = 0; g < 3; g++) {
         if (b->gstream[g]) { hipStreamSynchronize(b->gstream[g]); hipStreamDestroy(b->gstream[g]); }
         if (b->gevent[g]) hipEventDestroy(b->gevent[g]);
@@ -2436,10 +2434,10 @@ static int batch_create(gh_t **handles, int n, gh_batch_t **out, bool panel)
     b->cap_paths = 0;
     b->pipe_windows = b->pipe_aborted = 0;
     b->prof_every = 0; b->pused[0] = b->pused[1] = 0; b->prof_windows = 0; b->prof_bytes[0] = b->prof_bytes[1] = 0.0;
-    b->panel = panel; b->p_paths = nullptr; b->p_pcap = 0; b->pinfo_nt = b->pinfo_c = 0;
+    b->panel = panel; b->pinfo_nt = b->pinfo_c = 0;
     b->nb = (int)(((size_t)(b->N + 1) * (b->W > 8 ? b->W : 8) + 255) / 256);   // >= blocks of k_marg<.., true>
     hipError_t e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc((void **)&b->d_wd, sizeof(win_desc) * n * (panel ? 2 : 1));
+    if (e == hipSuccess) e = hipMalloc((void **)&b->d_wd, sizeof(win_desc) * n * 2);
     if (e == hipSuccess) e = hipMalloc((void **)&b->d_states, sizeof(dev_state) * n);
     if (e == hipSuccess) e = hipMalloc((void **)&b->d_partial, sizeof(double) * (size_t)b->nb * n);
     if (e != hipSuccess) { gh_batch_destroy(b); return fail(GH_ERR_NOMEM, "batch allocation failed: %s", hipGetErrorString(e)); }
@@ -2540,9 +2538,6 @@ static bool pipe_instantiated(int L, int nt)
     return false;
 }
 
-// the window pipeline over the windows `wd` describes: marginals, snapshot and the full table for every window (what the batched
-// launches do in front of their first path), then ONE launch that carries every window through all its paths (wpipe.hpp)
-// launch_only: the preamble has run (batch_pipe_preamble) and b->d_wd + d_off holds the n descriptors this launch takes
 // the pipeline's preamble over the n windows whose descriptors stand at gwd, on `st`: marginals, snapshot and the full table of every
 // window.  N, W: the largest window's -- they size the grids; every kernel takes its window's own shape from the descriptor
 static void pipe_preamble(const gh_handle *h0, hipStream_t st, const win_desc *gwd, int n, int N, int W, int L)
@@ -2591,67 +2586,12 @@ static pipe_params pipe_make_params(const gh_handle *h0, int N, int W, int L, in
     return P;
 }
 
-// the window pipeline over the windows `wd` describes: marginals, snapshot and the full table for every window (what the batched
-// launches do in front of their first path), then ONE launch that carries every window through all its paths (wpipe.hpp)
-// launch_only: the preamble has run (batch_pipe_preamble) and b->d_wd + d_off holds the n descriptors this launch takes
-static int batch_run_pipe(gh_batch *b, const std::vector<win_desc> &wd, int max_paths, double min_remove, int nt, bool launch_only = false, int d_off = 0, bool no_sync = false)
-{
-    const int n = (int)wd.size();
-    if (n == 0) return GH_OK;
-    if (!launch_only) HIPCHK(hipMemcpyAsync(b->d_wd, wd.data(), sizeof(win_desc) * n, hipMemcpyHostToDevice, b->stream));
-    gh_handle *h0 = b->hs[0];
-    const bool f64 = h0->cfg.storage == GH_STORAGE_F64;
-    const int N = b->N, W = b->W, L = b->L;
-    hipStream_t st = b->stream;
-    const win_desc *gwd = b->d_wd + d_off;
-    if (!launch_only) {
-    hipLaunchKernelGGL(k_batch_reset, dim3(n), dim3(64), 0, b->stream, (const win_desc *)b->d_wd);
-    HIPCHK(hipStreamSynchronize(b->stream));        // wd is a host temporary
-    pipe_preamble(h0, st, gwd, n, N, W, L);
-    HIPCHK(hipGetLastError());
-    if (nt == 0) return GH_OK;                      // (the preamble only: batch_pipe_preamble)
-    }
-    size_t lds = 0;
-    pipe_params P = pipe_make_params(h0, N, W, L, nt, false, max_paths, min_remove, &lds);
-    P.prof = (b->prof_every > 0 || getenv("GH_PIPE_STAMPS")) ? 1 : 0;
-    b->pused[0] = b->pused[1] = 0;
-    auto pmark = [&](hipStream_t s_) {
-        if (b->pused[0] >= b->pev[0].size()) {
-            hipEvent_t e;
-            if (hipEventCreate(&e) != hipSuccess) return;
-            b->pev[0].push_back(e);
-        }
-        hipEventRecord(b->pev[0][b->pused[0]++], s_);
-    };
-    const bool sample = b->prof_every > 0;
-    if (sample) { b->prof_windows = n; pmark(st); }
-    const hipError_t le = f64 ? launch_wpipe<double>(L, nt, P, gwd, n, lds, st) : launch_wpipe<float>(L, nt, P, gwd, n, lds, st);
-    if (le != hipSuccess) return fail(GH_ERR_HIP, "gh_batch_spin: the pipeline launch failed (L=%d, %d threads, %zu bytes of LDS): %s", L, nt, lds, hipGetErrorString(le));
-    if (sample) pmark(st);
-    if (!no_sync) HIPCHK(hipStreamSynchronize(st));
-    {
-        // algorithmic bytes per window over the whole launch, the pipeline's own accounting: per position
-        // and path the walk reads its compact table (4 rows x L lags x 32 bytes) and the bookkeeper the counts, the original
-        // log-marginals and the packed word (64 + 48 + 8) and writes a path byte; the sweep reads the W rows of the path's symbol
-        // (7 elements each), the counts and two packed words, writes W cells, two counts and min(L, W) x 32 bytes of table
-        const double es = f64 ? 8.0 : 4.0;
-        const int Lw = (h0->cfg.cond_mode == GH_COND_B || W >= L) ? L : W;
-        const double ext = (double)N * (128.0 * L + 64 + 48 + 8 + 1);
-        const double rw = (double)(N + 1) * (7.0 * es * W + es * W + 64 + 16 + 16 + 32.0 * Lw + 1);
-        b->prof_bytes[0] = (ext + rw) * max_paths;
-        b->prof_bytes[1] = 0.0;
-    }
-    return GH_OK;
-}
-
 // the batched launches of rounds 1-4 over the windows `wd` describes (a path = k_lt's flag check, one serial walker per window, the
 // fused reweight k_marg<T,true>, the removed mass); returns with every stream drained
 static int batch_run_launches(gh_batch *b, const std::vector<win_desc> &wd, int max_paths, double min_remove, bool reset = true)
 {
     const int n = (int)wd.size();
     if (n == 0) return GH_OK;
-    const size_t n1 = (size_t)b->N + 1;
-    (void)n1;
     HIPCHK(hipMemcpyAsync(b->d_wd, wd.data(), sizeof(win_desc) * n, hipMemcpyHostToDevice, b->stream));
     if (reset) hipLaunchKernelGGL(k_batch_reset, dim3(n), dim3(64), 0, b->stream, (const win_desc *)b->d_wd);
     HIPCHK(hipStreamSynchronize(b->stream));        // wd is a host temporary
@@ -2763,31 +2703,11 @@ static int batch_run_launches(gh_batch *b, const std::vector<win_desc> &wd, int 
     return GH_OK;
 }
 
-// the windows the narrow pipeline left untouched because a position offers five candidates: the WIDE pipeline (wpipe.hpp) over them --
-// marginals, snapshot and table stand (batch_run_pipe's preamble ran over every window); a window it cannot take either (too many such
-// positions) keeps PIPE_NOT_STARTED
-static int batch_run_pipe_wide(gh_batch *b, const std::vector<win_desc> &wd, int max_paths, double min_remove, int nt, hipStream_t stream = nullptr, int d_off = -1)
-{
-    const int n = (int)wd.size();
-    if (n == 0) return GH_OK;
-    gh_handle *h0 = b->hs[0];
-    const bool f64 = h0->cfg.storage == GH_STORAGE_F64;
-    const int N = b->N, W = b->W, L = b->L;
-    const bool own = d_off < 0;                     // (else: the descriptors stand at b->d_wd + d_off, the caller waits for `stream`)
-    if (own) { stream = b->stream; d_off = 0; HIPCHK(hipMemcpyAsync(b->d_wd, wd.data(), sizeof(win_desc) * n, hipMemcpyHostToDevice, b->stream)); }
-    size_t lds = 0;
-    const pipe_params P = pipe_make_params(h0, N, W, L, nt, true, max_paths, min_remove, &lds);
-    const hipError_t le = f64 ? launch_wpipe_w<double>(L, nt, P, b->d_wd + d_off, n, lds, stream) : launch_wpipe_w<float>(L, nt, P, b->d_wd + d_off, n, lds, stream);
-    if (le != hipSuccess) return fail(GH_ERR_HIP, "gh_batch_spin: the wide pipeline launch failed (L=%d, %d threads, %zu bytes of LDS): %s", L, nt, lds, hipGetErrorString(le));
-    if (own) HIPCHK(hipStreamSynchronize(b->stream));        // wd is a host temporary
-    return GH_OK;
-}
-
 // gh_spin over some windows of a batch from a few host threads, every window on its own stream (the windows' kernel chains
 // interleave on the GPU).  A job is (window, paths it already has): the spin writes the window's remaining paths behind them.
-// paths_off (panels): window w's paths stand at paths_out + paths_off[w], [max_paths][N_w + 1]; nullptr: [n][max_paths][N + 1]
+// Window w's paths stand at paths_out + paths_off[w], [max_paths][N_w + 1].
 static int batch_spin_on_streams(gh_batch *b, const std::vector<std::pair<int, int>> &jobs, int max_paths, double min_remove,
-                                 uint8_t *paths_out, gh_path_rec *recs, int *n_out, int *hole_at, const int64_t *paths_off = nullptr)
+                                 uint8_t *paths_out, const int64_t *paths_off, gh_path_rec *recs, int *n_out, int *hole_at)
 {
     const int nj = (int)jobs.size();
     if (nj == 0) return GH_OK;
@@ -2805,7 +2725,7 @@ static int batch_spin_on_streams(gh_batch *b, const std::vector<std::pair<int, i
             int n2 = 0, hole2 = 0;
             if (nd < max_paths) {
                 const size_t n1 = (size_t)b->hs[w]->N + 1;
-                uint8_t *pw = paths_off ? paths_out + paths_off[w] + n1 * nd : paths_out + n1 * ((size_t)max_paths * w + nd);
+                uint8_t *pw = paths_out + paths_off[w] + n1 * nd;
                 rcs[q] = gh_spin(b->hs[w], max_paths - nd, min_remove, pw, recs + (size_t)max_paths * w + nd, &n2, &hole2);
                 if (rcs[q]) errs[q] = gh_last_error();
             }
@@ -2822,476 +2742,436 @@ static int batch_spin_on_streams(gh_batch *b, const std::vector<std::pair<int, i
     return GH_OK;
 }
 
+// ---- the window pipeline's host driver: gh_batch_spin and gh_panel_spin both run it --------------------------------------------
+// GH_PIPE_STAMPS: the host phases of a spin on stderr
+struct spin_phases {
+    const char *who;
+    bool on;
+    double t;
+    static double now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+    explicit spin_phases(const char *w) : who(w), on(getenv("GH_PIPE_STAMPS") != nullptr), t(now()) {}
+    void operator()(const char *what)
+    {
+        if (!on) return;
+        const double t1 = now();
+        fprintf(stderr, "%s: %-28s %8.3f ms\n", who, what, t1 - t);
+        t = t1;
+    }
+};
+
+// both spins start here: every window's table allocated, and whatever the handles' own streams still carry (fills) done before the
+// batch's streams touch the tensors -- those streams, not the device: a device-wide wait also waits for whatever else the process
+// runs (ResultExchange's gather on its side stream in a multi-rank run)
+static int batch_spin_begin(gh_batch *b)
+{
+    int rc;
+    for (int w = 0; w < b->n; w++)
+        if ((rc = alloc_lt(b->hs[w]))) return rc;
+    for (int w = 0; w < b->n; w++) HIPCHK(hipStreamSynchronize(b->hs[w]->stream));
+    return GH_OK;
+}
+
+// where window w's paths stand in the batch's device buffer: [max_paths][N_w + 1] per window, back to back in window order (for a
+// batch [n][max_paths][N + 1], the caller's layout too); off[n] = the whole buffer
+static std::vector<int64_t> batch_path_offsets(const gh_batch *b, int max_paths)
+{
+    std::vector<int64_t> off((size_t)b->n + 1, 0);
+    for (int w = 0; w < b->n; w++) off[w + 1] = off[w] + ((int64_t)b->hs[w]->N + 1) * max_paths;
+    return off;
+}
+// the device homes of the results: paths at those offsets, records [n][max_paths]
+static int batch_buffers(gh_batch *b, int max_paths, const std::vector<int64_t> &off)
+{
+    if (max_paths <= b->cap_paths) return GH_OK;
+    HIPCHK(hipStreamSynchronize(b->stream));
+    hipFree(b->d_paths); hipFree(b->d_recs);
+    b->d_paths = nullptr; b->d_recs = nullptr; b->cap_paths = 0;
+    HIPCHK(hipMalloc((void **)&b->d_paths, (size_t)off[b->n]));
+    HIPCHK(hipMalloc((void **)&b->d_recs, sizeof(gh_path_rec) * (size_t)max_paths * b->n));
+    b->cap_paths = max_paths;
+    return GH_OK;
+}
+
+// window w's descriptor (kernels.hpp): its tensors and state, its share of the batch's buffers, the pipeline buffers it has
+static win_desc batch_desc(gh_batch *b, int w, int max_paths, const std::vector<int64_t> &off)
+{
+    gh_handle *h = b->hs[w];
+    win_desc d;
+    memset(&d, 0, sizeof(d));
+    d.band = h->band; d.cnt = h->cnt; d.marg = h->marg; d.minfo = h->minfo; d.nvalid = h->nvalid; d.cmask = h->cmask;
+    d.rinfo = h->need_rinfo ? h->rinfo : nullptr; d.G = h->lt; d.Ht = nullptr; d.Yt = nullptr; d.st = h->dstate;   // no walker tables in batches (kernels.hpp)
+    d.partial = b->d_partial + (size_t)w * b->nb;
+    d.paths = b->d_paths + off[w];
+    d.recs = b->d_recs + (size_t)max_paths * w;
+    d.snap = h->have_orig ? 0 : 1;       // the first batched k_marg is followed by a batched snapshot
+    d.pk = h->pipe_pk; d.gp = h->pipe_gp; d.lmr = h->pipe_lm; d.tband = h->tband; d.gw = h->pipe_gw;
+    d.wdir = h->pipe_gw ? reinterpret_cast<int *>(h->pipe_gw + (size_t)PIPE_WMAX * pipe_wrec_doubles(h->L)) : nullptr;
+    d.N = h->N; d.W = h->W;
+    h->have_orig = true;
+    return d;
+}
+
+// the states of the windows ws, whose descriptors stand at b->d_wd[0 ..) in that order, into hs[ws[i]]: one launch, one copy
+static int batch_gather_states(gh_batch *b, const std::vector<int> &ws, std::vector<dev_state> &hs)
+{
+    const int m = (int)ws.size();
+    if (m == 0) return GH_OK;
+    std::vector<dev_state> tmp(m);
+    hipLaunchKernelGGL(k_batch_states, dim3(m), dim3(64), 0, b->stream, (const win_desc *)b->d_wd, b->d_states);
+    HIPCHK(hipMemcpyAsync(tmp.data(), b->d_states, sizeof(dev_state) * m, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    for (int i = 0; i < m; i++) hs[ws[i]] = tmp[i];
+    return GH_OK;
+}
+
+// the pipeline's buffers of one window, at its own N and L; under the column conditionals also the to-major copy of the band,
+// brought in step with it on b->stream (the pipeline's sweep then keeps both, element by element)
+static int pipe_buffers(gh_batch *b, gh_handle *h)
+{
+    if (!h->pipe_pk) HIPCHK(hipMalloc((void **)&h->pipe_pk, sizeof(unsigned long long) * ((size_t)h->N + 2)));
+    const size_t need = sizeof(double) * ((size_t)h->N + LT_PAD) * 16 * (size_t)h->L;
+    if (h->pipe_gp_bytes < need) {
+        hipFree(h->pipe_gp); h->pipe_gp = nullptr; h->pipe_gp_bytes = 0;
+        HIPCHK(hipMalloc((void **)&h->pipe_gp, need));
+        h->pipe_gp_bytes = need;
+    }
+    if (h->cfg.marginal_term && !h->pipe_lm) HIPCHK(hipMalloc((void **)&h->pipe_lm, sizeof(double) * 4 * ((size_t)h->N + 2)));
+    if (h->cfg.cond_mode == GH_COND_C || h->cfg.cond_mode == GH_COND_E) {
+        const size_t nel = h->n_cells * CELL;
+        if (!h->tband && hipMalloc(&h->tband, nel * esize(h)) != hipSuccess) { h->tband = nullptr; return fail(GH_ERR_NOMEM, "hipMalloc for the to-major band failed"); }
+        if (h->tband_epoch != h->band_epoch) {
+            const unsigned nbt = (unsigned)((nel + 255) / 256);
+            if (h->cfg.storage == GH_STORAGE_F64) hipLaunchKernelGGL(k_band_to_major<double>, dim3(nbt), dim3(256), 0, b->stream, (const double *)h->band, (double *)h->tband, nel, h->W);
+            else hipLaunchKernelGGL(k_band_to_major<float>, dim3(nbt), dim3(256), 0, b->stream, (const float *)h->band, (float *)h->tband, nel, h->W);
+            h->tband_epoch = h->band_epoch;
+        }
+    }
+    return GH_OK;
+}
+
+// windows the pipeline carries together: one lag count (it is instantiated per lag count), sized by the largest window
+struct pipe_group { int L, nt, N, W; std::vector<int> ws; };
+
+// The window pipeline (wpipe.hpp) takes row and column conditionals with or without the marginal term, 2..14 lags, a path that fits
+// the LDS beside the walker's tables; from GH_PIPE_MIN windows on (a window alone runs at one walker's pace, ~2 000 paths/s: below two
+// dozen windows the segment-parallel spins on their own streams are faster).  GH_PIPE=0: none.  The windows go in one group per L;
+// a window joins its group if its spec and the sweep's 32-bit element offsets allow, a group runs if it has enough windows and a chunk
+// at its largest N.  `left` gets the windows no group takes.  A batch (one L) makes at most one group.  Also clears what
+// gh_batch_pipe_info reports: the spin that follows sets it.
+static std::vector<pipe_group> pipe_groups(gh_batch *b, std::vector<int> &left)
+{
+    const gh_handle *h0 = b->hs[0];
+    const int pipe_env = getenv("GH_PIPE") ? atoi(getenv("GH_PIPE")) : 1;
+    const int pipe_min = getenv("GH_PIPE_MIN") ? atoi(getenv("GH_PIPE_MIN")) : 24;
+    const int bwm0 = h0->wmode == WM_SEG ? WM_SPEC : h0->wmode;
+    const int es = h0->cfg.storage == GH_STORAGE_F64 ? 8 : 4, mt = h0->cfg.marginal_term ? 1 : 0;
+    b->pipe_windows = b->pipe_aborted = b->pinfo_nt = b->pinfo_c = 0;
+    std::map<int, std::vector<int>> byL;
+    for (int w = 0; w < b->n; w++) byL[b->hs[w]->L].push_back(w);
+    std::vector<pipe_group> groups;
+    for (auto &kv : byL) {
+        pipe_group g{kv.first, pipe_threads(kv.first), 0, 0, {}};
+        const bool ok = pipe_env && g.nt && pipe_instantiated(g.L, g.nt) && walk_depth2_ok(bwm0, g.L);
+        for (int w : kv.second) {
+            const gh_handle *h = b->hs[w];
+            if (ok && pipe_spec_ok(h) && (unsigned long long)(h->N + 2) * 49ull * (unsigned long long)h->W < (1ull << 31)) {
+                g.ws.push_back(w);
+                if (h->N > g.N) g.N = h->N;
+                if (h->W > g.W) g.W = h->W;
+            } else left.push_back(w);
+        }
+        if (!g.ws.empty() && (int)g.ws.size() >= pipe_min && pipe_chunk(g.N, g.L, pipe_sweep_threads(g.nt), es, mt) > 0) groups.push_back(std::move(g));
+        else left.insert(left.end(), g.ws.begin(), g.ws.end());
+    }
+    return groups;
+}
+
+// The window pipeline over the groups' windows: their buffers and descriptors (into wd), one reset, each group's preamble (marginals,
+// snapshot, full table) on one of the batch's four streams, one gather of the control words; then per group the narrow launch over
+// its ranked windows and the WIDE one over those in which a position offers five candidates (deletion columns), round robin over the
+// same streams, and a second gather (into hs).  Which launch takes a window is only known once its marginals stand: hence the one
+// host round trip between the two phases (~30 us).  GH_PIPE_WIDE=0: the narrow launches alone.  not_started: the windows no launch
+// took (a hole; too many five-candidate positions for the WIDE launch's records; any five-candidate window without the WIDE launch);
+// later gets (window, paths done) of those the pipeline stopped at a moved candidate mask: paths 0 .. n_done-1 are complete and
+// reweighted, gh_spin takes the rest.  Records the windows carried and handed back, and the threads and chunk of the group with the
+// most windows, whose narrow launch gh_batch_profile_* brackets.
+static int pipe_spin_groups(gh_batch *b, const std::vector<pipe_group> &groups, int max_paths, double min_remove,
+                            const std::vector<int64_t> &off, std::vector<win_desc> &wd, std::vector<dev_state> &hs,
+                            std::vector<int> &not_started, std::vector<std::pair<int, int>> &later, spin_phases &phase)
+{
+    const int n = b->n;
+    gh_handle *h0 = b->hs[0];
+    const bool f64 = h0->cfg.storage == GH_STORAGE_F64;
+    const int es = f64 ? 8 : 4, mt = h0->cfg.marginal_term ? 1 : 0;
+    const bool wide_env = !(getenv("GH_PIPE_WIDE") && atoi(getenv("GH_PIPE_WIDE")) == 0);
+    int rc;
+    for (int g = 0; g < 3; g++)
+        if (!b->gstream[g]) HIPCHK(hipStreamCreateWithFlags(&b->gstream[g], hipStreamNonBlocking));
+    const hipStream_t streams[4] = {b->stream, b->gstream[0], b->gstream[1], b->gstream[2]};
+    // every pipeline window's descriptor, group by group at d_wd[0 .. np); ord[i] = the window of descriptor i
+    std::vector<win_desc> all;
+    std::vector<int> ord, gfirst;
+    size_t big = 0;
+    for (size_t gi = 0; gi < groups.size(); gi++) {
+        gfirst.push_back((int)ord.size());
+        for (int w : groups[gi].ws) {
+            if ((rc = pipe_buffers(b, b->hs[w]))) return rc;
+            wd[w] = batch_desc(b, w, max_paths, off);
+            all.push_back(wd[w]);
+            ord.push_back(w);
+        }
+        if (groups[gi].ws.size() > groups[big].ws.size()) big = gi;
+    }
+    const int np = (int)ord.size();
+    phase("descriptors");
+    HIPCHK(hipMemcpyAsync(b->d_wd, all.data(), sizeof(win_desc) * np, hipMemcpyHostToDevice, b->stream));
+    hipLaunchKernelGGL(k_batch_reset, dim3(np), dim3(64), 0, b->stream, (const win_desc *)b->d_wd);
+    HIPCHK(hipStreamSynchronize(b->stream));
+    for (size_t gi = 0; gi < groups.size(); gi++) {
+        const pipe_group &g = groups[gi];
+        pipe_preamble(h0, streams[gi % 4], b->d_wd + gfirst[gi], (int)g.ws.size(), g.N, g.W, g.L);
+    }
+    HIPCHK(hipGetLastError());
+    for (int s = 0; s < 4; s++) HIPCHK(hipStreamSynchronize(streams[s]));
+    if ((rc = batch_gather_states(b, ord, hs))) return rc;
+    // the launches: per group the narrow one and the WIDE one, their descriptor lists at d_wd[n ..], launch k on stream k % 4
+    struct plaunch { int gi; bool wide; int off, cnt; };
+    std::vector<plaunch> launches;
+    std::vector<win_desc> lists;
+    std::vector<char> listed(n, 0);
+    for (size_t gi = 0; gi < groups.size(); gi++) {
+        const pipe_group &g = groups[gi];
+        const bool wide_on = wide_env && pipe_wide_instantiated(g.L, g.nt) && !h0->cfg.offer_zero &&
+                             pipe_chunk_w(g.N, g.L, pipe_sweep_threads(g.nt), es, mt) > 0;
+        std::vector<win_desc> nar, wid;
+        for (int w : g.ws) {
+            gh_handle *h = b->hs[w];
+            const bool live = !hs[w].stop && hs[w].first_hole > h->N;
+            if (live && hs[w].ranked != 0 && hs[w].narrow != 0) { nar.push_back(wd[w]); listed[w] = 1; }
+            else if (live && hs[w].ranked == 0 && wide_on && h->N < 65536) {
+                const size_t need = pipe_gw_bytes(h->N, h->L);
+                if (h->pipe_gw_bytes < need) {
+                    hipFree(h->pipe_gw); h->pipe_gw = nullptr; h->pipe_gw_bytes = 0;
+                    HIPCHK(hipMalloc((void **)&h->pipe_gw, need));
+                    h->pipe_gw_bytes = need;
+                }
+                wd[w].gw = h->pipe_gw;
+                wd[w].wdir = reinterpret_cast<int *>(h->pipe_gw + (size_t)PIPE_WMAX * pipe_wrec_doubles(h->L));
+                wid.push_back(wd[w]);
+                listed[w] = 1;
+            }
+        }
+        if (!nar.empty()) { launches.push_back({(int)gi, false, n + (int)lists.size(), (int)nar.size()}); lists.insert(lists.end(), nar.begin(), nar.end()); }
+        if (!wid.empty()) { launches.push_back({(int)gi, true, n + (int)lists.size(), (int)wid.size()}); lists.insert(lists.end(), wid.begin(), wid.end()); }
+    }
+    if (!lists.empty()) HIPCHK(hipMemcpyAsync(b->d_wd + n, lists.data(), sizeof(win_desc) * lists.size(), hipMemcpyHostToDevice, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    b->pused[0] = b->pused[1] = 0;
+    auto pmark = [&](hipStream_t st) {            // one event of the start/stop pair around the largest group's narrow launch
+        if (b->pused[0] >= b->pev[0].size()) {
+            hipEvent_t e;
+            if (hipEventCreate(&e) != hipSuccess) return;
+            b->pev[0].push_back(e);
+        }
+        hipEventRecord(b->pev[0][b->pused[0]++], st);
+    };
+    for (size_t k = 0; k < launches.size(); k++) {
+        const plaunch &q = launches[k];
+        const pipe_group &g = groups[q.gi];
+        const hipStream_t st = streams[k % 4];
+        const bool mark = !q.wide && q.gi == (int)big;
+        size_t lds = 0;
+        pipe_params P = pipe_make_params(h0, g.N, g.W, g.L, g.nt, q.wide, max_paths, min_remove, &lds);
+        if (mark) P.prof = (b->prof_every > 0 || getenv("GH_PIPE_STAMPS")) ? 1 : 0;
+        if (mark && b->prof_every > 0) { b->prof_windows = q.cnt; pmark(st); }
+        const win_desc *gwd = b->d_wd + q.off;
+        hipError_t le;
+        if (q.wide) le = f64 ? launch_wpipe_w<double>(g.L, g.nt, P, gwd, q.cnt, lds, st) : launch_wpipe_w<float>(g.L, g.nt, P, gwd, q.cnt, lds, st);
+        else le = f64 ? launch_wpipe<double>(g.L, g.nt, P, gwd, q.cnt, lds, st) : launch_wpipe<float>(g.L, g.nt, P, gwd, q.cnt, lds, st);
+        if (le != hipSuccess)
+            return fail(GH_ERR_HIP, "%s: the %s pipeline launch failed (L=%d, %d threads, %zu bytes of LDS): %s", phase.who, q.wide ? "wide" : "narrow",
+                        g.L, g.nt, lds, hipGetErrorString(le));
+        if (mark && b->prof_every > 0) pmark(st);
+        if (mark) {
+            // algorithmic bytes per window over the whole launch, the pipeline's own accounting: per position
+            // and path the walk reads its compact table (4 rows x L lags x 32 bytes) and the bookkeeper the counts, the original
+            // log-marginals and the packed word (64 + 48 + 8) and writes a path byte; the sweep reads the W rows of the path's symbol
+            // (7 elements each), the counts and two packed words, writes W cells, two counts and min(L, W) x 32 bytes of table
+            const int Lw = (h0->cfg.cond_mode == GH_COND_B || g.W >= g.L) ? g.L : g.W;
+            const double ext = (double)g.N * (128.0 * g.L + 64 + 48 + 8 + 1);
+            const double rw = (double)(g.N + 1) * (7.0 * es * g.W + es * g.W + 64 + 16 + 16 + 32.0 * Lw + 1);
+            b->prof_bytes[0] = (ext + rw) * max_paths;
+            b->prof_bytes[1] = 0.0;
+        }
+    }
+    for (int s = 0; s < 4; s++) HIPCHK(hipStreamSynchronize(streams[s]));
+    phase("preamble + pipeline kernel");
+    if ((rc = batch_gather_states(b, ord, hs))) return rc;
+    phase("states to host");
+    for (int w : ord) {
+        if (!listed[w]) hs[w].pipe_status = PIPE_NOT_STARTED;
+        if (hs[w].pipe_status == PIPE_NOT_STARTED) not_started.push_back(w);
+        else if (hs[w].pipe_status == PIPE_ABORTED) { later.emplace_back(w, hs[w].n_done); b->pipe_aborted++; }
+        else if (hs[w].pipe_status != PIPE_DONE) return fail(GH_ERR_STATE, "%s: window %d left the pipeline in state %d", phase.who, w, hs[w].pipe_status);
+    }
+    b->pipe_windows = np - (int)not_started.size();
+    b->pinfo_nt = groups[big].nt;
+    b->pinfo_c = pipe_chunk(groups[big].N, groups[big].L, pipe_sweep_threads(groups[big].nt), es, mt);
+    if (getenv("GH_PIPE_STAMPS")) {         // 100 MHz ticks per path as the bookkeepers of a few windows saw them
+        for (int i = 0; i < np; i += (np > 4 ? np / 4 : 1)) {
+            const int w = ord[i];
+#ifdef PIPE_PROF
+            fprintf(stderr, "pipe window %d, Mcycles (work, own memory, barrier): sweeper %.2f %.2f %.2f  loader %.2f %.2f %.2f  bookkeeper %.2f %.2f %.2f\n", w,
+                    hs[w].dbg8[0] / 1e6, hs[w].dbg8[1] / 1e6, hs[w].dbg8[2] / 1e6, hs[w].dbg8[3] / 1e6, hs[w].dbg8[4] / 1e6, hs[w].dbg8[5] / 1e6,
+                    hs[w].dbg8[6] / 1e6, hs[w].dbg8[7] / 1e6, hs[w].dbg8[8] / 1e6);
+            fprintf(stderr, "walker: %.2f Mcycles walking, %.2f at its barriers; bookkeeper: %.2f per-position part, %.2f sequential sums\n", hs[w].dbg8[10] / 1e6, hs[w].dbg8[11] / 1e6, hs[w].dbg[0] / 1e6, hs[w].dbg[1] / 1e6);
+            fprintf(stderr, "wide walker: %.2f Mcycles in %llu groups by the exact stepper, %.2f Mcycles inside the speculative blocks, %llu primes\n", (double)(hs[w].dbg[2] & ((1ull << 40) - 1)) / 1e6,
+                    (unsigned long long)(hs[w].dbg[2] >> 40), (double)(hs[w].dbg[3] & ((1ull << 40) - 1)) / 1e6, (unsigned long long)(hs[w].dbg[3] >> 40));
+            fprintf(stderr, "SIMD of waves 0..15:");
+            for (int q = 0; q < 16; q++) fprintf(stderr, " %d", (int)((hs[w].dbg8[9] >> (2 * q)) & 3));
+            fprintf(stderr, "\n");
+            break;
+#else
+            fprintf(stderr, "pipe window %d, us per path:", w);
+            for (int q = 0; q < 12 && q < max_paths; q++) fprintf(stderr, " %.1f", (double)hs[w].dbg8[q] / 100.0);
+            fprintf(stderr, "\n");
+#endif
+        }
+    }
+    return GH_OK;
+}
+
+// what the device computed for the windows ws (ascending) to the caller: paths in runs of windows that lie back to back on both sides,
+// records [n][max_paths]; then each window's outcome and flags -- its tensor has changed, marginals and table are rebuilt from it on
+// next use, the to-major band stays in step where the pipeline's sweep wrote both
+static int batch_finish(gh_batch *b, const std::vector<int> &ws, const std::vector<dev_state> &hs, int max_paths, const std::vector<int64_t> &off,
+                        uint8_t *paths_out, const int64_t *paths_off, gh_path_rec *recs, int *n_out, int *hole_at)
+{
+    for (size_t i = 0; i < ws.size();) {
+        const int w = ws[i];
+        size_t j = i + 1;
+        while (j < ws.size() && ws[j] == ws[j - 1] + 1 && paths_off[ws[j]] - paths_off[w] == off[ws[j]] - off[w]) j++;
+        const int e = ws[j - 1] + 1;
+        HIPCHK(hipMemcpyAsync(paths_out + paths_off[w], b->d_paths + off[w], (size_t)(off[e] - off[w]), hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipMemcpyAsync(recs + (size_t)max_paths * w, b->d_recs + (size_t)max_paths * w, sizeof(gh_path_rec) * (size_t)max_paths * (e - w),
+                              hipMemcpyDeviceToHost, b->stream));
+        i = j;
+    }
+    HIPCHK(hipStreamSynchronize(b->stream));
+    for (int w : ws) {
+        gh_handle *h = b->hs[w];
+        n_out[w] = hs[w].n_done;
+        hole_at[w] = hs[w].stop ? hs[w].hole_at : 0;
+        const bool kept = h->tband && h->tband_epoch == h->band_epoch &&
+                          (hs[w].pipe_status == PIPE_DONE || hs[w].pipe_status == PIPE_ABORTED) &&
+                          (h->cfg.cond_mode == GH_COND_C || h->cfg.cond_mode == GH_COND_E);
+        h->dirty_marg = h->dirty_lt = true; h->band_epoch++;
+        if (kept) h->tband_epoch = h->band_epoch;       // (the pipeline's sweep wrote both)
+        h->lt_inc_path = nullptr;       // the batch reweighted many paths and maintains no walker tables: rebuild in full
+    }
+    return GH_OK;
+}
+
 extern "C" int gh_batch_spin(gh_batch_t *b, int max_paths, double min_remove, uint8_t *paths_out,
                              gh_path_rec *recs, int *n_out, int *hole_at)
 {
     if (!b || !paths_out || !recs || !n_out || !hole_at || max_paths < 1) return fail(GH_ERR_ARG, "bad argument");
     if (b->panel) return fail(GH_ERR_ARG, "gh_batch_spin: this is a panel (gh_panel_create): spin it with gh_panel_spin");
     HIPCHK(hipSetDevice(b->dev));
-    const bool hprof = getenv("GH_PIPE_STAMPS") != nullptr;        // host phases of this call on stderr
-    auto tnow = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double tph = tnow();
-    auto phase = [&](const char *what) { if (hprof) { const double t = tnow(); fprintf(stderr, "gh_batch_spin: %-28s %8.3f ms\n", what, t - tph); tph = t; } };
+    spin_phases phase("gh_batch_spin");
     const int n = b->n;
-    const size_t n1 = (size_t)b->N + 1;
     int rc;
-    for (int w = 0; w < n; w++) {
-        gh_handle *h = b->hs[w];
-        if (h->L != b->hs[0]->L)
-            return fail(GH_ERR_STATE, "window %d has L=%d but window 0 has L=%d: set one L (gh_set_L) for the batch", w, h->L, b->hs[0]->L);
-        if ((rc = alloc_lt(h))) return rc;
-    }
-    // whatever the handles' own streams still carry (fills) must be done before the batch's stream touches the tensors -- those
-    // streams, not the device: a device-wide wait also waits for whatever else the process runs (ResultExchange's gather on its
-    // side stream in a multi-rank run)
-    for (int w = 0; w < n; w++) HIPCHK(hipStreamSynchronize(b->hs[w]->stream));
+    for (int w = 0; w < n; w++)
+        if (b->hs[w]->L != b->hs[0]->L)
+            return fail(GH_ERR_STATE, "window %d has L=%d but window 0 has L=%d: set one L (gh_set_L) for the batch", w, b->hs[w]->L, b->hs[0]->L);
+    if ((rc = batch_spin_begin(b))) return rc;
     b->L = b->hs[0]->L;
     phase("tables allocated, device idle");
     // (measured on C3, MI355X: 8 windows 37k haplotypes/s this way against ~16k batched; 32 windows 45k either way -- the
     // chip is then busy with k_seg; from 48 windows on the batched serial walkers, one workgroup per window, win: 114k at 256)
     // (read on every call: the tests switch between the two ways; -1 = always the batched kernels)
     const int batch_cut = getenv("GH_BATCH_STREAMS_MAX") ? atoi(getenv("GH_BATCH_STREAMS_MAX")) : 47;
-    // The window pipeline (wpipe.hpp): row conditionals without the marginal term, 2..14 lags, a path that fits the LDS beside the
-    // walker's tables; from GH_PIPE_MIN windows on (a window alone runs at one walker's pace, ~2 000 paths/s: below two dozen
-    // windows the segment-parallel spins on their own streams are faster).  GH_PIPE=0: the batched launches of rounds 1-4.
-    int pipe_nt = 0;
-    {
-        gh_handle *h0 = b->hs[0];
-        const int pipe_env = getenv("GH_PIPE") ? atoi(getenv("GH_PIPE")) : 1;
-        const int pipe_min = getenv("GH_PIPE_MIN") ? atoi(getenv("GH_PIPE_MIN")) : 24;
-        const int bwm0 = h0->wmode == WM_SEG ? WM_SPEC : h0->wmode;
-        const int nt = pipe_threads(b->L);
-        if (pipe_env && n >= pipe_min && nt && pipe_instantiated(b->L, nt) && walk_depth2_ok(bwm0, b->L) && pipe_spec_ok(h0) &&
-            (unsigned long long)(b->N + 2) * 49ull * (unsigned long long)b->W < (1ull << 31) &&      // (the sweep's 32-bit element offsets)
-            pipe_chunk(b->N, b->L, pipe_sweep_threads(nt), h0->cfg.storage == GH_STORAGE_F64 ? 8 : 4, h0->cfg.marginal_term) > 0)
-            pipe_nt = nt;
-    }
-    if (!pipe_nt && batch_cut >= 0 &&
-        ((seg_ok(b->hs[0]->wmode, b->L) && n <= batch_cut) || cw_ok(b->hs[0]->wmode, b->L))) {
+    const bool seg = seg_ok(b->hs[0]->wmode, b->L), cw = cw_ok(b->hs[0]->wmode, b->L);
+    std::vector<int> rest;                      // windows no pipeline group takes, then those it leaves PIPE_NOT_STARTED
+    const std::vector<pipe_group> groups = pipe_groups(b, rest);
+    const std::vector<int64_t> off = batch_path_offsets(b, max_paths);
+    std::vector<std::pair<int, int>> later;     // (window, paths done): windows gh_spin finishes on their own streams behind the batch's copy
+    if (groups.empty() && batch_cut >= 0 && ((seg && n <= batch_cut) || cw)) {
         // The segment-parallel extensions fill the chip poorly with ONE window (four small dependent kernels per path, most
         // of their time launch and first-touch latency) but every window has its own stream: a few host threads each
         // run gh_spin over their share of the windows, and the windows' kernel chains interleave on the GPU.
-        std::vector<std::pair<int, int>> jobs;
-        for (int w = 0; w < n; w++) jobs.emplace_back(w, 0);
-        return batch_spin_on_streams(b, jobs, max_paths, min_remove, paths_out, recs, n_out, hole_at);
+        for (int w = 0; w < n; w++) later.emplace_back(w, 0);
+        return batch_spin_on_streams(b, later, max_paths, min_remove, paths_out, off.data(), recs, n_out, hole_at);
     }
-    if (max_paths > b->cap_paths) {
-        HIPCHK(hipStreamSynchronize(b->stream));
-        hipFree(b->d_paths); hipFree(b->d_recs);
-        b->d_paths = nullptr; b->d_recs = nullptr; b->cap_paths = 0;
-        HIPCHK(hipMalloc((void **)&b->d_paths, n1 * max_paths * n));
-        HIPCHK(hipMalloc((void **)&b->d_recs, sizeof(gh_path_rec) * (size_t)max_paths * n));
-        b->cap_paths = max_paths;
-    }
-    if (pipe_nt)
-        for (int w = 0; w < n; w++) {
-            gh_handle *h = b->hs[w];
-            if (!h->pipe_pk) HIPCHK(hipMalloc((void **)&h->pipe_pk, sizeof(unsigned long long) * ((size_t)b->N + 2)));
-            const size_t need = sizeof(double) * ((size_t)b->N + LT_PAD) * 16 * (size_t)b->L;
-            if (h->pipe_gp_bytes < need) {
-                hipFree(h->pipe_gp); h->pipe_gp = nullptr; h->pipe_gp_bytes = 0;
-                HIPCHK(hipMalloc((void **)&h->pipe_gp, need));
-                h->pipe_gp_bytes = need;
-            }
-            if (h->cfg.marginal_term && !h->pipe_lm) HIPCHK(hipMalloc((void **)&h->pipe_lm, sizeof(double) * 4 * ((size_t)b->N + 2)));
-            if (h->cfg.cond_mode == GH_COND_C || h->cfg.cond_mode == GH_COND_E) {
-                // the to-major copy of the band, in step with it (the pipeline's sweep then keeps both, element by element)
-                const size_t nel = h->n_cells * CELL;
-                if (!h->tband && hipMalloc(&h->tband, nel * esize(h)) != hipSuccess) { h->tband = nullptr; return fail(GH_ERR_NOMEM, "hipMalloc for the to-major band failed"); }
-                if (h->tband_epoch != h->band_epoch) {
-                    const unsigned nbt = (unsigned)((nel + 255) / 256);
-                    if (h->cfg.storage == GH_STORAGE_F64) hipLaunchKernelGGL(k_band_to_major<double>, dim3(nbt), dim3(256), 0, b->stream, (const double *)h->band, (double *)h->tband, nel, h->W);
-                    else hipLaunchKernelGGL(k_band_to_major<float>, dim3(nbt), dim3(256), 0, b->stream, (const float *)h->band, (float *)h->tband, nel, h->W);
-                    h->tband_epoch = h->band_epoch;
-                }
-            }
-        }
+    if ((rc = batch_buffers(b, max_paths, off))) return rc;
     std::vector<win_desc> wd(n);
-    for (int w = 0; w < n; w++) {
-        gh_handle *h = b->hs[w];
-        wd[w].band = h->band; wd[w].cnt = h->cnt; wd[w].marg = h->marg; wd[w].minfo = h->minfo;
-        wd[w].nvalid = h->nvalid; wd[w].cmask = h->cmask; wd[w].rinfo = h->need_rinfo ? h->rinfo : nullptr; wd[w].G = h->lt; wd[w].Ht = nullptr; wd[w].Yt = nullptr; wd[w].st = h->dstate;   // no walker tables in batches (kernels.hpp)
-        wd[w].partial = b->d_partial + (size_t)w * b->nb;
-        wd[w].paths = b->d_paths + n1 * max_paths * w;
-        wd[w].recs = b->d_recs + (size_t)max_paths * w;
-        wd[w].snap = h->have_orig ? 0 : 1;       // the first batched k_marg is followed by a batched snapshot
-        wd[w]._pad = 0;
-        wd[w].pk = h->pipe_pk;
-        wd[w].gp = h->pipe_gp;
-        wd[w].lmr = h->pipe_lm;
-        wd[w].tband = h->tband;
-        wd[w].gw = h->pipe_gw;
-        wd[w].wdir = h->pipe_gw ? reinterpret_cast<int *>(h->pipe_gw + (size_t)PIPE_WMAX * pipe_wrec_doubles(b->L)) : nullptr;
-        wd[w].N = h->N; wd[w].W = h->W;
-        h->have_orig = true;
-    }
     std::vector<dev_state> hs(n);
-    auto fetch_states = [&]() -> int {
-        // (b->d_wd may describe a sub-list by now: the gather takes the full list again)
-        HIPCHK(hipMemcpyAsync(b->d_wd, wd.data(), sizeof(win_desc) * n, hipMemcpyHostToDevice, b->stream));
-        hipLaunchKernelGGL(k_batch_states, dim3(n), dim3(64), 0, b->stream, (const win_desc *)b->d_wd, b->d_states);
-        HIPCHK(hipMemcpyAsync(hs.data(), b->d_states, sizeof(dev_state) * n, hipMemcpyDeviceToHost, b->stream));
-        HIPCHK(hipStreamSynchronize(b->stream));
-        return GH_OK;
-    };
-    std::vector<int> aborted;           // windows whose pipeline stopped at a moved candidate mask: gh_spin takes their remaining paths
-    std::vector<std::pair<int, int>> later;     // (window, paths done): windows gh_spin finishes on their own streams behind the batch's copy
-    b->pipe_windows = 0;
-    phase("descriptors");
-    if (pipe_nt) {
-        // Windows in which a position offers five candidates (deletion columns) go to the pipeline's WIDE launch (wpipe.hpp), the
-        // others to the narrow one -- side by side on two streams: which is which is only known once the marginals stand, so the
-        // preamble runs first and the host looks at the states (one wait, 30 us).  GH_PIPE_WIDE=0: the narrow launch alone, what it
-        // leaves goes to the batched launches as until round 5.
-        gh_handle *hp0 = b->hs[0];
-        const bool wide_on = !(getenv("GH_PIPE_WIDE") && atoi(getenv("GH_PIPE_WIDE")) == 0) && pipe_wide_instantiated(b->L, pipe_nt) &&
-                             !hp0->cfg.offer_zero && b->N < 65536 &&
-                             pipe_chunk_w(b->N, b->L, pipe_sweep_threads(pipe_nt), hp0->cfg.storage == GH_STORAGE_F64 ? 8 : 4, hp0->cfg.marginal_term) > 0;
-        std::vector<win_desc> both;             // (the descriptors of the two launches: alive until both have ended)
-        std::vector<char> listed((size_t)n, 1);
-        if (!wide_on) {
-            if ((rc = batch_run_pipe(b, wd, max_paths, min_remove, pipe_nt))) return rc;
-        } else {
-            if ((rc = batch_run_pipe(b, wd, max_paths, min_remove, 0))) return rc;          // reset + marginals, snapshot, table
-            if ((rc = fetch_states())) return rc;
-            std::vector<win_desc> nar, wid;
-            const size_t need = pipe_gw_bytes(b->N, b->L);
-            for (int w = 0; w < n; w++) {
-                const bool live = !hs[w].stop && hs[w].first_hole > b->N;
-                if (live && hs[w].ranked != 0 && hs[w].narrow != 0) nar.push_back(wd[w]);
-                else if (live && hs[w].ranked == 0) {
-                    gh_handle *h = b->hs[w];
-                    if (h->pipe_gw_bytes < need) {
-                        hipFree(h->pipe_gw); h->pipe_gw = nullptr; h->pipe_gw_bytes = 0;
-                        HIPCHK(hipMalloc((void **)&h->pipe_gw, need));
-                        h->pipe_gw_bytes = need;
-                    }
-                    wd[w].gw = h->pipe_gw;
-                    wd[w].wdir = reinterpret_cast<int *>(h->pipe_gw + (size_t)PIPE_WMAX * pipe_wrec_doubles(b->L));
-                    wid.push_back(wd[w]);
-                } else listed[(size_t)w] = 0;       // (a hole: neither launch takes it)
-            }
-            both = nar;
-            both.insert(both.end(), wid.begin(), wid.end());
-            if (!both.empty()) HIPCHK(hipMemcpyAsync(b->d_wd, both.data(), sizeof(win_desc) * both.size(), hipMemcpyHostToDevice, b->stream));
-            HIPCHK(hipStreamSynchronize(b->stream));
-            if (!wid.empty() && !b->gstream[0]) HIPCHK(hipStreamCreateWithFlags(&b->gstream[0], hipStreamNonBlocking));
-            if (!nar.empty() && (rc = batch_run_pipe(b, nar, max_paths, min_remove, pipe_nt, true, 0, true))) return rc;
-            if (!wid.empty() && (rc = batch_run_pipe_wide(b, wid, max_paths, min_remove, pipe_nt, b->gstream[0], (int)nar.size()))) return rc;
-            HIPCHK(hipStreamSynchronize(b->stream));
-            if (!wid.empty()) HIPCHK(hipStreamSynchronize(b->gstream[0]));
-        }
-        phase("preamble + pipeline kernel");
-        if ((rc = fetch_states())) return rc;
-        for (int w = 0; w < n; w++)
-            if (!listed[(size_t)w]) hs[w].pipe_status = PIPE_NOT_STARTED;
-        phase("states to host");
-        std::vector<win_desc> rest;     // not eligible when the kernel looked (a position offers five candidates, a hole): the batched launches
-        for (int w = 0; w < n; w++) {
-            if (hs[w].pipe_status == PIPE_NOT_STARTED) rest.push_back(wd[w]);
-            else if (hs[w].pipe_status == PIPE_ABORTED) aborted.push_back(w);
-            else if (hs[w].pipe_status != PIPE_DONE) return fail(GH_ERR_STATE, "gh_batch_spin: window %d left the pipeline in state %d", w, hs[w].pipe_status);
-        }
-        b->pipe_windows = n - (int)rest.size();
-        auto print_stamps = [&]() {
-        if (getenv("GH_PIPE_STAMPS")) {         // 100 MHz ticks per path as the bookkeepers of a few windows saw them
-            for (int w = 0; w < n; w += (n > 4 ? n / 4 : 1)) {
-#ifdef PIPE_PROF
-                fprintf(stderr, "pipe window %d, Mcycles (work, own memory, barrier): sweeper %.2f %.2f %.2f  loader %.2f %.2f %.2f  bookkeeper %.2f %.2f %.2f\n", w,
-                        hs[w].dbg8[0] / 1e6, hs[w].dbg8[1] / 1e6, hs[w].dbg8[2] / 1e6, hs[w].dbg8[3] / 1e6, hs[w].dbg8[4] / 1e6, hs[w].dbg8[5] / 1e6,
-                        hs[w].dbg8[6] / 1e6, hs[w].dbg8[7] / 1e6, hs[w].dbg8[8] / 1e6);
-                fprintf(stderr, "walker: %.2f Mcycles walking, %.2f at its barriers; bookkeeper: %.2f per-position part, %.2f sequential sums\n", hs[w].dbg8[10] / 1e6, hs[w].dbg8[11] / 1e6, hs[w].dbg[0] / 1e6, hs[w].dbg[1] / 1e6);
-                fprintf(stderr, "wide walker: %.2f Mcycles in %llu groups by the exact stepper, %.2f Mcycles inside the speculative blocks, %llu primes\n", (double)(hs[w].dbg[2] & ((1ull << 40) - 1)) / 1e6,
-                        (unsigned long long)(hs[w].dbg[2] >> 40), (double)(hs[w].dbg[3] & ((1ull << 40) - 1)) / 1e6, (unsigned long long)(hs[w].dbg[3] >> 40));
-                fprintf(stderr, "SIMD of waves 0..15:");
-                for (int q = 0; q < 16; q++) fprintf(stderr, " %d", (int)((hs[w].dbg8[9] >> (2 * q)) & 3));
-                fprintf(stderr, "\n");
-                break;
-#else
-                fprintf(stderr, "pipe window %d, us per path:", w);
-                for (int q = 0; q < 12 && q < max_paths; q++) fprintf(stderr, " %.1f", (double)hs[w].dbg8[q] / 100.0);
-                fprintf(stderr, "\n");
-#endif
-            }
-        }
-        };
-        print_stamps();
-        // What the two launches left untouched (a hole; too many five-candidate positions for the WIDE launch's records; every
-        // five-candidate window under GH_PIPE_WIDE=0).  A FEW such windows go the
-        // single window's way, each on its own stream from a few host threads -- the segment-parallel / candidate-pool spins (mixed
-        // radix at five lags): 25-37k haplotypes/s where the batched serial walkers, one wavefront per window, give 16k for eight
-        // windows; from four dozen on the batched launches over all of them.
-        if (!rest.empty() && batch_cut >= 0 && (int)rest.size() <= batch_cut && (seg_ok(b->hs[0]->wmode, b->L) || cw_ok(b->hs[0]->wmode, b->L))) {
-            for (int w = 0; w < n; w++)
-                if (hs[w].pipe_status == PIPE_NOT_STARTED) later.emplace_back(w, 0);
+    if (!groups.empty()) {
+        std::vector<int> not_started;
+        if ((rc = pipe_spin_groups(b, groups, max_paths, min_remove, off, wd, hs, not_started, later, phase))) return rc;
+        rest.insert(rest.end(), not_started.begin(), not_started.end());
+        // What the pipeline left (a hole; too many five-candidate positions for the WIDE launch's records; every five-candidate
+        // window under GH_PIPE_WIDE=0).  A FEW such windows go the single window's way, each on its own stream from a few host
+        // threads -- the segment-parallel / candidate-pool spins (mixed radix at five lags): 25-37k haplotypes/s where the batched
+        // serial walkers, one wavefront per window, give 16k for eight windows; from four dozen on the batched launches over all of them.
+        if (!rest.empty() && batch_cut >= 0 && (int)rest.size() <= batch_cut && (seg || cw)) {
+            for (int w : rest) later.emplace_back(w, 0);
             rest.clear();
         }
-        if (!rest.empty()) {
-            if ((rc = batch_run_launches(b, rest, max_paths, min_remove))) return rc;
-            if ((rc = fetch_states())) return rc;
+    }
+    if (!rest.empty()) {
+        std::sort(rest.begin(), rest.end());
+        std::vector<win_desc> rd;
+        for (int w : rest) {
+            if (!wd[w].st) wd[w] = batch_desc(b, w, max_paths, off);       // (not one of the pipeline's windows)
+            rd.push_back(wd[w]);
         }
-    } else {
-        if ((rc = batch_run_launches(b, wd, max_paths, min_remove))) return rc;
-        if ((rc = fetch_states())) return rc;
+        if ((rc = batch_run_launches(b, rd, max_paths, min_remove))) return rc;
+        if ((rc = batch_gather_states(b, rest, hs))) return rc;
     }
-    HIPCHK(hipMemcpyAsync(paths_out, b->d_paths, n1 * max_paths * n, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipMemcpyAsync(recs, b->d_recs, sizeof(gh_path_rec) * (size_t)max_paths * n, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
+    std::vector<int> every(n);
+    for (int w = 0; w < n; w++) every[w] = w;
+    if ((rc = batch_finish(b, every, hs, max_paths, off, paths_out, off.data(), recs, n_out, hole_at))) return rc;
     phase("paths and records to host");
-    for (int w = 0; w < n; w++) {
-        n_out[w] = hs[w].n_done;
-        hole_at[w] = hs[w].stop ? hs[w].hole_at : 0;
-        const bool kept = b->hs[w]->tband && b->hs[w]->tband_epoch == b->hs[w]->band_epoch && pipe_nt &&
-                          (hs[w].pipe_status == PIPE_DONE || hs[w].pipe_status == PIPE_ABORTED) &&
-                          (b->hs[w]->cfg.cond_mode == GH_COND_C || b->hs[w]->cfg.cond_mode == GH_COND_E);
-        b->hs[w]->dirty_marg = b->hs[w]->dirty_lt = true; b->hs[w]->band_epoch++;
-        if (kept) b->hs[w]->tband_epoch = b->hs[w]->band_epoch;       // (the pipeline's sweep wrote both)
-        b->hs[w]->lt_inc_path = nullptr;       // the batch reweighted many paths and maintains no walker tables: rebuild in full
-    }
-    // aborted windows: paths 0 .. n_done-1 are complete and reweighted; marginals and table are rebuilt from the tensor (dirty flags
-    // above).  In a deep spin many windows stop once counts reach zero: they, and the few the pipeline did not take, are finished
-    // side by side (one after the other on the calling thread they were the tail of the batch)
-    for (int w : aborted) later.emplace_back(w, hs[w].n_done);
-    if ((rc = batch_spin_on_streams(b, later, max_paths, min_remove, paths_out, recs, n_out, hole_at))) return rc;
-    b->pipe_aborted = (int)aborted.size();
-    return GH_OK;
+    // In a deep spin many windows stop once counts reach zero: they, and the few the pipeline did not take, are finished side by
+    // side (one after the other on the calling thread they were the tail of the batch)
+    return batch_spin_on_streams(b, later, max_paths, min_remove, paths_out, off.data(), recs, n_out, hole_at);
 }
 
 // ---- panels: windows of differing N, W and L (gh_panel_*) ----------------------------------------------------------------------
-// The windows go in one GROUP per lag count L (the pipeline is instantiated per lag count).  A group the pipeline can carry -- the
-// eligibility test gh_batch_spin makes, over the group's own windows -- runs the pipeline's preamble and launches, sized by its
-// largest window, on one of the batch's four streams; every kernel takes its window's own N and W from the descriptor.  What no
-// group carries (a group too small, a lag count beyond the pipeline, a hole, too many five-candidate positions, the remaining paths
-// of an aborted window) is finished by gh_spin window by window on its own stream, as in gh_batch_spin.
+// The window pipeline carries every group it can (pipe_groups, pipe_spin_groups); every kernel takes its window's own N and W from
+// the descriptor.  What no group carries (a group too small, a lag count beyond the pipeline, a hole, too many five-candidate
+// positions, the remaining paths of an aborted window) is finished by gh_spin window by window on its own stream.
 extern "C" int gh_panel_spin(gh_batch_t *b, int max_paths, double min_remove, uint8_t *paths_out, const int64_t *paths_off,
                              gh_path_rec *recs, int *n_out, int *hole_at)
 {
     if (!b || !paths_out || !paths_off || !recs || !n_out || !hole_at || max_paths < 1) return fail(GH_ERR_ARG, "bad argument");
     if (!b->panel) return fail(GH_ERR_ARG, "gh_panel_spin: not a panel (gh_panel_create)");
     HIPCHK(hipSetDevice(b->dev));
+    spin_phases phase("gh_panel_spin");
     const int n = b->n;
     int rc;
-    for (int w = 0; w < n; w++) {
-        if (paths_off[w] < 0) return fail(GH_ERR_ARG, "gh_panel_spin: window %d has a negative path offset", w);
-        if ((rc = alloc_lt(b->hs[w]))) return rc;
-    }
-    for (int w = 0; w < n; w++) HIPCHK(hipStreamSynchronize(b->hs[w]->stream));     // (the handles' fills: see gh_batch_spin)
-    gh_handle *h0 = b->hs[0];
-    const bool f64 = h0->cfg.storage == GH_STORAGE_F64;
-    const int es = f64 ? 8 : 4, mt = h0->cfg.marginal_term ? 1 : 0;
-    const int pipe_env = getenv("GH_PIPE") ? atoi(getenv("GH_PIPE")) : 1;
-    const int pipe_min = getenv("GH_PIPE_MIN") ? atoi(getenv("GH_PIPE_MIN")) : 24;
-    const bool wide_env = !(getenv("GH_PIPE_WIDE") && atoi(getenv("GH_PIPE_WIDE")) == 0);
-    const int bwm0 = h0->wmode == WM_SEG ? WM_SPEC : h0->wmode;
-    struct pgroup { int L, nt, N, W; std::vector<int> ws; };
-    std::vector<pgroup> groups;
-    std::vector<std::pair<int, int>> later;     // (window, paths done): gh_spin finishes them
-    {
-        std::map<int, std::vector<int>> byL;
-        for (int w = 0; w < n; w++) byL[b->hs[w]->L].push_back(w);
-        for (auto &kv : byL) {
-            pgroup g;
-            g.L = kv.first; g.nt = pipe_threads(g.L); g.N = 0; g.W = 0;
-            const bool ok = pipe_env && g.nt && pipe_instantiated(g.L, g.nt) && walk_depth2_ok(bwm0, g.L);
-            for (int w : kv.second) {
-                const gh_handle *h = b->hs[w];
-                if (ok && pipe_spec_ok(h) && (unsigned long long)(h->N + 2) * 49ull * (unsigned long long)h->W < (1ull << 31)) {   // (the sweep's 32-bit element offsets)
-                    g.ws.push_back(w);
-                    if (h->N > g.N) g.N = h->N;
-                    if (h->W > g.W) g.W = h->W;
-                } else later.emplace_back(w, 0);
-            }
-            if (!g.ws.empty() && (int)g.ws.size() >= pipe_min && pipe_chunk(g.N, g.L, pipe_sweep_threads(g.nt), es, mt) > 0) groups.push_back(g);
-            else for (int w : g.ws) later.emplace_back(w, 0);
-        }
-    }
-    std::vector<int> grp(n, -1);
-    for (size_t gi = 0; gi < groups.size(); gi++)
-        for (int w : groups[gi].ws) grp[w] = (int)gi;
-    // the pipeline's paths, [window][max_paths][N_w + 1] in window order; its records as gh_batch_spin's, [n][max_paths]
-    std::vector<size_t> doff(n, 0);
-    size_t ptot = 0;
     for (int w = 0; w < n; w++)
-        if (grp[w] >= 0) { doff[w] = ptot; ptot += ((size_t)b->hs[w]->N + 1) * max_paths; }
-    b->pipe_windows = b->pipe_aborted = 0;
-    b->pinfo_nt = b->pinfo_c = 0;
-    b->pused[0] = b->pused[1] = 0;
-    std::vector<dev_state> hs(n);
+        if (paths_off[w] < 0) return fail(GH_ERR_ARG, "gh_panel_spin: window %d has a negative path offset", w);
+    if ((rc = batch_spin_begin(b))) return rc;
+    std::vector<int> left;
+    const std::vector<pipe_group> groups = pipe_groups(b, left);
+    std::vector<std::pair<int, int>> later;     // (window, paths done): gh_spin finishes them
+    for (int w : left) later.emplace_back(w, 0);
     if (!groups.empty()) {
-        if (ptot > b->p_pcap) {
-            HIPCHK(hipStreamSynchronize(b->stream));
-            hipFree(b->p_paths); b->p_paths = nullptr; b->p_pcap = 0;
-            HIPCHK(hipMalloc((void **)&b->p_paths, ptot));
-            b->p_pcap = ptot;
-        }
-        if (max_paths > b->cap_paths) {
-            HIPCHK(hipStreamSynchronize(b->stream));
-            hipFree(b->d_recs); b->d_recs = nullptr; b->cap_paths = 0;
-            HIPCHK(hipMalloc((void **)&b->d_recs, sizeof(gh_path_rec) * (size_t)max_paths * n));
-            b->cap_paths = max_paths;
-        }
-        for (int g = 0; g < 3; g++)
-            if (!b->gstream[g]) HIPCHK(hipStreamCreateWithFlags(&b->gstream[g], hipStreamNonBlocking));
-        const hipStream_t streams[4] = {b->stream, b->gstream[0], b->gstream[1], b->gstream[2]};
-        // per-window buffers of the pipeline (gh_batch_spin's, at the window's own N and L)
-        for (int w = 0; w < n; w++) {
-            if (grp[w] < 0) continue;
-            gh_handle *h = b->hs[w];
-            if (!h->pipe_pk) HIPCHK(hipMalloc((void **)&h->pipe_pk, sizeof(unsigned long long) * ((size_t)h->N + 2)));
-            const size_t need = sizeof(double) * ((size_t)h->N + LT_PAD) * 16 * (size_t)h->L;
-            if (h->pipe_gp_bytes < need) {
-                hipFree(h->pipe_gp); h->pipe_gp = nullptr; h->pipe_gp_bytes = 0;
-                HIPCHK(hipMalloc((void **)&h->pipe_gp, need));
-                h->pipe_gp_bytes = need;
-            }
-            if (h->cfg.marginal_term && !h->pipe_lm) HIPCHK(hipMalloc((void **)&h->pipe_lm, sizeof(double) * 4 * ((size_t)h->N + 2)));
-            if (h->cfg.cond_mode == GH_COND_C || h->cfg.cond_mode == GH_COND_E) {
-                const size_t nel = h->n_cells * CELL;
-                if (!h->tband && hipMalloc(&h->tband, nel * esize(h)) != hipSuccess) { h->tband = nullptr; return fail(GH_ERR_NOMEM, "hipMalloc for the to-major band failed"); }
-                if (h->tband_epoch != h->band_epoch) {
-                    const unsigned nbt = (unsigned)((nel + 255) / 256);
-                    if (f64) hipLaunchKernelGGL(k_band_to_major<double>, dim3(nbt), dim3(256), 0, b->stream, (const double *)h->band, (double *)h->tband, nel, h->W);
-                    else hipLaunchKernelGGL(k_band_to_major<float>, dim3(nbt), dim3(256), 0, b->stream, (const float *)h->band, (float *)h->tband, nel, h->W);
-                    h->tband_epoch = h->band_epoch;
-                }
-            }
-        }
-        // every pipeline window's descriptor, group by group (d_wd[0 .. np)); ord[i] = the window of descriptor i
+        const std::vector<int64_t> off = batch_path_offsets(b, max_paths);
+        if ((rc = batch_buffers(b, max_paths, off))) return rc;
         std::vector<win_desc> wd(n);
-        std::vector<int> ord, gfirst;
-        for (const pgroup &g : groups) {
-            gfirst.push_back((int)ord.size());
-            for (int w : g.ws) {
-                gh_handle *h = b->hs[w];
-                win_desc &d = wd[w];
-                memset(&d, 0, sizeof(d));
-                d.band = h->band; d.cnt = h->cnt; d.marg = h->marg; d.minfo = h->minfo; d.nvalid = h->nvalid; d.cmask = h->cmask;
-                d.rinfo = h->need_rinfo ? h->rinfo : nullptr; d.G = h->lt; d.Ht = nullptr; d.Yt = nullptr; d.st = h->dstate;
-                d.partial = b->d_partial + (size_t)w * b->nb;
-                d.paths = b->p_paths + doff[w];
-                d.recs = b->d_recs + (size_t)max_paths * w;
-                d.snap = h->have_orig ? 0 : 1;
-                d.pk = h->pipe_pk; d.gp = h->pipe_gp; d.lmr = h->pipe_lm; d.tband = h->tband; d.gw = h->pipe_gw;
-                d.wdir = h->pipe_gw ? reinterpret_cast<int *>(h->pipe_gw + (size_t)PIPE_WMAX * pipe_wrec_doubles(h->L)) : nullptr;
-                d.N = h->N; d.W = h->W;
-                h->have_orig = true;
-                ord.push_back(w);
-            }
-        }
-        const int np = (int)ord.size();
-        std::vector<win_desc> all(np);
-        for (int i = 0; i < np; i++) all[i] = wd[ord[i]];
-        {
-            HIPCHK(hipMemcpyAsync(b->d_wd, all.data(), sizeof(win_desc) * np, hipMemcpyHostToDevice, b->stream));
-            hipLaunchKernelGGL(k_batch_reset, dim3(np), dim3(64), 0, b->stream, (const win_desc *)b->d_wd);
-            HIPCHK(hipStreamSynchronize(b->stream));
-            // the preambles, group g on stream g % 4 (sized by the group's largest window)
-            for (size_t gi = 0; gi < groups.size(); gi++) {
-                const pgroup &g = groups[gi];
-                pipe_preamble(h0, streams[gi % 4], b->d_wd + gfirst[gi], (int)g.ws.size(), g.N, g.W, g.L);
-            }
-            HIPCHK(hipGetLastError());
-            for (int s = 0; s < 4; s++) HIPCHK(hipStreamSynchronize(streams[s]));
-        }
-        {
-            std::vector<dev_state> tmp(np);
-            HIPCHK(hipMemcpyAsync(b->d_wd, all.data(), sizeof(win_desc) * np, hipMemcpyHostToDevice, b->stream));
-            hipLaunchKernelGGL(k_batch_states, dim3(np), dim3(64), 0, b->stream, (const win_desc *)b->d_wd, b->d_states);
-            HIPCHK(hipMemcpyAsync(tmp.data(), b->d_states, sizeof(dev_state) * np, hipMemcpyDeviceToHost, b->stream));
-            HIPCHK(hipStreamSynchronize(b->stream));
-            for (int i = 0; i < np; i++) hs[ord[i]] = tmp[i];
-        }
-        // the launches: per group the narrow one over its ranked windows and the WIDE one over those with five-candidate
-        // positions; their descriptor lists at d_wd[n ..], launch k on stream k % 4
-        struct plaunch { int gi; bool wide; int off, cnt; };
-        std::vector<plaunch> launches;
-        std::vector<win_desc> lists;
-        std::vector<char> listed(n, 0);
-        for (size_t gi = 0; gi < groups.size(); gi++) {
-            const pgroup &g = groups[gi];
-            const bool wide_on = wide_env && pipe_wide_instantiated(g.L, g.nt) && !h0->cfg.offer_zero &&
-                                 pipe_chunk_w(g.N, g.L, pipe_sweep_threads(g.nt), es, mt) > 0;
-            std::vector<win_desc> nar, wid;
-            for (int w : g.ws) {
-                const bool live = !hs[w].stop && hs[w].first_hole > b->hs[w]->N;
-                if (live && hs[w].ranked != 0 && hs[w].narrow != 0) { nar.push_back(wd[w]); listed[w] = 1; }
-                else if (live && hs[w].ranked == 0 && wide_on && b->hs[w]->N < 65536) {
-                    gh_handle *h = b->hs[w];
-                    const size_t need = pipe_gw_bytes(h->N, h->L);
-                    if (h->pipe_gw_bytes < need) {
-                        hipFree(h->pipe_gw); h->pipe_gw = nullptr; h->pipe_gw_bytes = 0;
-                        HIPCHK(hipMalloc((void **)&h->pipe_gw, need));
-                        h->pipe_gw_bytes = need;
-                    }
-                    wd[w].gw = h->pipe_gw;
-                    wd[w].wdir = reinterpret_cast<int *>(h->pipe_gw + (size_t)PIPE_WMAX * pipe_wrec_doubles(h->L));
-                    wid.push_back(wd[w]);
-                    listed[w] = 1;
-                }
-            }
-            if (!nar.empty()) { launches.push_back({(int)gi, false, n + (int)lists.size(), (int)nar.size()}); lists.insert(lists.end(), nar.begin(), nar.end()); }
-            if (!wid.empty()) { launches.push_back({(int)gi, true, n + (int)lists.size(), (int)wid.size()}); lists.insert(lists.end(), wid.begin(), wid.end()); }
-        }
-        if (!lists.empty()) HIPCHK(hipMemcpyAsync(b->d_wd + n, lists.data(), sizeof(win_desc) * lists.size(), hipMemcpyHostToDevice, b->stream));
-        HIPCHK(hipStreamSynchronize(b->stream));
-        int most = 0;
-        for (size_t k = 0; k < launches.size(); k++) {
-            const plaunch &q = launches[k];
-            const pgroup &g = groups[q.gi];
-            const hipStream_t st = streams[k % 4];
-            size_t lds = 0;
-            const pipe_params P = pipe_make_params(h0, g.N, g.W, g.L, g.nt, q.wide, max_paths, min_remove, &lds);
-            const win_desc *gwd = b->d_wd + q.off;
-            hipError_t le;
-            if (q.wide) le = f64 ? launch_wpipe_w<double>(g.L, g.nt, P, gwd, q.cnt, lds, st) : launch_wpipe_w<float>(g.L, g.nt, P, gwd, q.cnt, lds, st);
-            else le = f64 ? launch_wpipe<double>(g.L, g.nt, P, gwd, q.cnt, lds, st) : launch_wpipe<float>(g.L, g.nt, P, gwd, q.cnt, lds, st);
-            if (le != hipSuccess)
-                return fail(GH_ERR_HIP, "gh_panel_spin: the %s pipeline launch failed (L=%d, %d threads, %zu bytes of LDS): %s", q.wide ? "wide" : "narrow",
-                            g.L, g.nt, lds, hipGetErrorString(le));
-            if (!q.wide && q.cnt > most) { most = q.cnt; b->pinfo_nt = g.nt; b->pinfo_c = P.C; }
-        }
-        for (int s = 0; s < 4; s++) HIPCHK(hipStreamSynchronize(streams[s]));
-        {
-            std::vector<dev_state> tmp(np);
-            hipLaunchKernelGGL(k_batch_states, dim3(np), dim3(64), 0, b->stream, (const win_desc *)b->d_wd, b->d_states);
-            HIPCHK(hipMemcpyAsync(tmp.data(), b->d_states, sizeof(dev_state) * np, hipMemcpyDeviceToHost, b->stream));
-            HIPCHK(hipStreamSynchronize(b->stream));
-            for (int i = 0; i < np; i++) hs[ord[i]] = tmp[i];
-        }
-        for (int w = 0; w < n; w++) {
-            if (grp[w] < 0) continue;
-            if (!listed[w]) hs[w].pipe_status = PIPE_NOT_STARTED;
-            if (hs[w].pipe_status == PIPE_NOT_STARTED) later.emplace_back(w, 0);
-            else if (hs[w].pipe_status == PIPE_ABORTED) { later.emplace_back(w, hs[w].n_done); b->pipe_aborted++; b->pipe_windows++; }
-            else if (hs[w].pipe_status == PIPE_DONE) b->pipe_windows++;
-            else return fail(GH_ERR_STATE, "gh_panel_spin: window %d left the pipeline in state %d", w, hs[w].pipe_status);
-        }
-        // the pipeline's paths and records to the caller, in runs of windows that lie back to back on both sides
-        for (int w = 0; w < n;) {
-            if (grp[w] < 0) { w++; continue; }
-            int e = w + 1;
-            while (e < n && grp[e] >= 0 && paths_off[e] - paths_off[w] == (int64_t)(doff[e] - doff[w])) e++;
-            const size_t bytes = doff[e - 1] + ((size_t)b->hs[e - 1]->N + 1) * max_paths - doff[w];
-            HIPCHK(hipMemcpyAsync(paths_out + paths_off[w], b->p_paths + doff[w], bytes, hipMemcpyDeviceToHost, b->stream));
-            HIPCHK(hipMemcpyAsync(recs + (size_t)max_paths * w, b->d_recs + (size_t)max_paths * w, sizeof(gh_path_rec) * (size_t)max_paths * (e - w),
-                                  hipMemcpyDeviceToHost, b->stream));
-            w = e;
-        }
-        HIPCHK(hipStreamSynchronize(b->stream));
-        for (int w = 0; w < n; w++) {
-            if (grp[w] < 0) continue;
-            gh_handle *h = b->hs[w];
-            n_out[w] = hs[w].n_done;
-            hole_at[w] = hs[w].stop ? hs[w].hole_at : 0;
-            const bool kept = h->tband && h->tband_epoch == h->band_epoch &&
-                              (hs[w].pipe_status == PIPE_DONE || hs[w].pipe_status == PIPE_ABORTED) &&
-                              (h->cfg.cond_mode == GH_COND_C || h->cfg.cond_mode == GH_COND_E);
-            h->dirty_marg = h->dirty_lt = true; h->band_epoch++;
-            if (kept) h->tband_epoch = h->band_epoch;       // (the pipeline's sweep wrote both)
-            h->lt_inc_path = nullptr;
-        }
+        std::vector<dev_state> hs(n);
+        std::vector<int> not_started, ws;
+        if ((rc = pipe_spin_groups(b, groups, max_paths, min_remove, off, wd, hs, not_started, later, phase))) return rc;
+        for (int w : not_started) later.emplace_back(w, 0);
+        for (const pipe_group &g : groups) ws.insert(ws.end(), g.ws.begin(), g.ws.end());
+        std::sort(ws.begin(), ws.end());
+        if ((rc = batch_finish(b, ws, hs, max_paths, off, paths_out, paths_off, recs, n_out, hole_at))) return rc;
+        phase("paths and records to host");
     }
-    return batch_spin_on_streams(b, later, max_paths, min_remove, paths_out, recs, n_out, hole_at, paths_off);
+    return batch_spin_on_streams(b, later, max_paths, min_remove, paths_out, paths_off, recs, n_out, hole_at);
 }
 
 extern "C" int gh_host_alloc(size_t bytes, void **out)
@@ -3312,14 +3192,8 @@ extern "C" int gh_batch_pipe_info(gh_batch_t *b, int32_t out[4])
 {
     if (!b || !out) return fail(GH_ERR_ARG, "bad argument");
     out[0] = b->pipe_windows; out[1] = b->pipe_aborted;
-    if (b->panel) {
-        out[2] = b->pipe_windows ? b->pinfo_nt : 0;
-        out[3] = b->pipe_windows ? b->pinfo_c : 0;
-        return GH_OK;
-    }
-    const int nt = pipe_threads(b->L);
-    out[2] = b->pipe_windows ? nt : 0;
-    out[3] = b->pipe_windows ? pipe_chunk(b->N, b->L, pipe_sweep_threads(nt), b->hs[0]->cfg.storage == GH_STORAGE_F64 ? 8 : 4, b->hs[0]->cfg.marginal_term) : 0;
+    out[2] = b->pipe_windows ? b->pinfo_nt : 0;
+    out[3] = b->pipe_windows ? b->pinfo_c : 0;
     return GH_OK;
 }
 

@@ -500,8 +500,11 @@ class HanselBatch:
         self._lib = self.hansels[0]._lib
         arr = (C.c_void_p * len(self.hansels))(*[h._h for h in self.hansels])
         b = C.c_void_p()
-        check(self._lib.gh_batch_create(arr, len(self.hansels), C.byref(b)))
+        check(self._create(arr, len(self.hansels), C.byref(b)))
         self._b = b
+
+    def _create(self, arr, n, out):
+        return self._lib.gh_batch_create(arr, n, out)
 
     def __del__(self):
         try:
@@ -531,41 +534,51 @@ class HanselBatch:
             out[name] = dict(ms=ms.value, launches=n.value, windows=w.value, bytes_per_launch=by.value)
         return out
 
-    def _host_buffers(self, n, max_paths, n1):
+    def _host_buffers(self, max_paths):
         """Page-locked result buffers, kept from call to call (gh_host_alloc): the copies of 256 windows x 100 paths run at the
-        link's rate and no 256 MB array is faulted in per call.  Every block is owned by a _PinnedBlock that the arrays made over
-        it keep alive: a view handed out by spin(copy=False) stays valid memory for as long as anything refers to it, also when
-        the batch has moved on to buffers of another shape or is gone (they used to point at freed pinned memory)."""
-        key = (n, max_paths, n1)
+        link's rate and no 256 MB array is faulted in per call.  Window w's paths are max_paths rows of n_w + 1 bytes from
+        self._hb_off[w], back to back (for a batch: [n][max_paths][n + 1]); self._hb_win[w] is that [max_paths][n_w + 1] view.
+        Every block is owned by a _PinnedBlock that the arrays made over it keep alive: a view handed out by spin(copy=False)
+        stays valid memory for as long as anything refers to it, also when the batch has moved on to buffers of another shape or
+        is gone (they used to point at freed pinned memory)."""
+        n1s = tuple(h.n + 1 for h in self.hansels)
+        key = (max_paths, n1s)
         if getattr(self, "_hb_key", None) != key:
             self._free_host_buffers()
-            sizes = (n * max_paths * n1, n * max_paths * 5 * 8)
+            n = len(n1s)
+            off = np.zeros(n, dtype=np.int64)
+            off[1:] = np.cumsum(np.asarray(n1s[:-1], dtype=np.int64) * max_paths)
+            sizes = (sum(n1s) * max_paths, n * max_paths * 5 * 8)
             blocks = [_PinnedBlock(self._lib, max(1, sz)) for sz in sizes]
-            self._hb_paths = blocks[0].array(np.uint8, sizes[0]).reshape(n, max_paths, n1)
+            self._hb_paths = blocks[0].array(np.uint8, sizes[0])
             self._hb_recs = blocks[1].array(np.float64, sizes[1] // 8).reshape(n, max_paths, 5)
+            self._hb_off = off
+            self._hb_win = [self._hb_paths[o:o + max_paths * k].reshape(max_paths, k) for o, k in zip(off.tolist(), n1s)]
             self._hb_key = key
         return self._hb_paths, self._hb_recs
 
     def _free_host_buffers(self):
         # (the blocks free themselves when the last array over them is gone)
-        self._hb_key, self._hb_paths, self._hb_recs = None, None, None
+        self._hb_key, self._hb_paths, self._hb_recs, self._hb_off, self._hb_win = None, None, None, None, None
+
+    def _spin(self, max_paths, min_remove, paths, recs, n_out, hole):
+        check(self._lib.gh_batch_spin(self._b, int(max_paths), float(min_remove), _p(paths), _p(recs), _p(n_out), _p(hole)))
 
     def spin(self, max_paths=100, min_remove=0.01, copy=True):
-        """copy=False: the returned arrays are views of the batch's page-locked buffers (no 256 MB copy on the host); their
-        CONTENTS stand until the next spin() of this batch overwrites them, the memory itself for as long as a view refers to it.
-        copy=True (default): every window gets its own arrays."""
+        """One dict per window, the keys and dtypes of Hansel.spin.  copy=False: the returned arrays are views of the batch's
+        page-locked buffers (no 256 MB copy on the host); their CONTENTS stand until the next spin() of this batch overwrites
+        them, the memory itself for as long as a view refers to it.  copy=True (default): every window gets its own arrays."""
         n = len(self.hansels)
-        n1 = self.hansels[0].n + 1
-        paths, recs = self._host_buffers(n, max_paths, n1)
+        paths, recs = self._host_buffers(max_paths)
         n_out = np.zeros(n, dtype=np.int32)
         hole = np.zeros(n, dtype=np.int32)
-        check(self._lib.gh_batch_spin(self._b, int(max_paths), float(min_remove), _p(paths), _p(recs), _p(n_out), _p(hole)))
+        self._spin(max_paths, min_remove, paths, recs, n_out, hole)
         out = []
         for w in range(n):
             k = int(n_out[w])
             if k:
                 self.hansels[w].is_weighted = True
-            pw, rw = paths[w, :k], recs[w, :k]
+            pw, rw = self._hb_win[w][:k], recs[w, :k]
             if copy:
                 pw, rw = pw.copy(), rw.copy()
             out.append(dict(n=k, hole_at=int(hole[w]), paths=pw, hp_current=rw[:, 0], hp_original=rw[:, 1], ratio=rw[:, 2],
@@ -579,57 +592,12 @@ class HanselPanel(HanselBatch):
     the rest.  Every window's results are those of its Hansel.spin alone.  The Hansels must already be filled and agree on
     storage, modes and device."""
 
-    def __init__(self, hansels):
-        self.hansels = list(hansels)
-        if not self.hansels:
-            raise ValueError("empty panel")
-        for h in self.hansels:
-            h._ensure()
-        self._lib = self.hansels[0]._lib
-        arr = (C.c_void_p * len(self.hansels))(*[h._h for h in self.hansels])
-        b = C.c_void_p()
-        check(self._lib.gh_panel_create(arr, len(self.hansels), C.byref(b)))
-        self._b = b
+    def _create(self, arr, n, out):
+        return self._lib.gh_panel_create(arr, n, out)
 
-    def _host_buffers(self, n, max_paths, n1s):
-        """Page-locked result buffers as HanselBatch's: window w's paths are rows of n1s[w] bytes from self._hb_off[w]."""
-        key = (n, max_paths, tuple(n1s))
-        if getattr(self, "_hb_key", None) != key:
-            self._free_host_buffers()
-            off = np.zeros(n, dtype=np.int64)
-            if n > 1:
-                off[1:] = np.cumsum(np.asarray(n1s[:-1], dtype=np.int64) * max_paths)
-            sizes = (int(sum(n1s)) * max_paths, n * max_paths * 5 * 8)
-            blocks = [_PinnedBlock(self._lib, max(1, sz)) for sz in sizes]
-            self._hb_paths = blocks[0].array(np.uint8, sizes[0])
-            self._hb_recs = blocks[1].array(np.float64, sizes[1] // 8).reshape(n, max_paths, 5)
-            self._hb_off = off
-            self._hb_key = key
-        return self._hb_paths, self._hb_recs
-
-    def spin(self, max_paths=100, min_remove=0.01, copy=True):
-        """One dict per window, the keys and dtypes of Hansel.spin.  copy=False: views of the panel's page-locked buffers (see
-        HanselBatch.spin)."""
-        n = len(self.hansels)
-        n1s = [h.n + 1 for h in self.hansels]
-        paths, recs = self._host_buffers(n, max_paths, n1s)
-        off = self._hb_off
-        n_out = np.zeros(n, dtype=np.int32)
-        hole = np.zeros(n, dtype=np.int32)
-        check(self._lib.gh_panel_spin(self._b, int(max_paths), float(min_remove), _p(paths), _p(off), _p(recs), _p(n_out), _p(hole)))
-        out = []
-        for w in range(n):
-            k = int(n_out[w])
-            if k:
-                self.hansels[w].is_weighted = True
-            o = int(off[w])
-            pw = paths[o:o + max_paths * n1s[w]].reshape(max_paths, n1s[w])[:k]
-            rw = recs[w, :k]
-            if copy:
-                pw, rw = pw.copy(), rw.copy()
-            out.append(dict(n=k, hole_at=int(hole[w]), paths=pw, hp_current=rw[:, 0], hp_original=rw[:, 1], ratio=rw[:, 2],
-                            magnitude=rw[:, 3], min_marginal=rw[:, 4]))
-        return out
+    def _spin(self, max_paths, min_remove, paths, recs, n_out, hole):
+        check(self._lib.gh_panel_spin(self._b, int(max_paths), float(min_remove), _p(paths), _p(self._hb_off), _p(recs), _p(n_out),
+                                      _p(hole)))
 
 
 class DeviceReads:
