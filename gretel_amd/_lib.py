@@ -49,6 +49,11 @@ class gh_path_rec(C.Structure):
                 ("ratio", C.c_double), ("magnitude", C.c_double), ("min_marginal", C.c_double)]
 
 
+class gh_assign_stats(C.Structure):
+    _fields_ = [("n_reads", C.c_int64), ("n_informative", C.c_int64), ("n_unique", C.c_int64), ("n_ambiguous", C.c_int64),
+                ("n_unexplained", C.c_int64)]
+
+
 _lib = None
 
 
@@ -120,6 +125,7 @@ def load():
         "gh_profile_overhead": [vp, i32, vp],
         "gh_debug_walk_clock": [vp, vp],
         "gh_debug_pool_geometry": [i32, i32, i32, vp],
+        "gh_assign_reads": [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, P(gh_assign_stats)],
         "gh_coverage_sites": [i32, vp, vp, vp, i64, C.c_int32, C.c_int32, C.c_int32, vp, vp],
     }
     for name, args in sigs.items():

@@ -7,6 +7,10 @@ Files written (formats: docs/protocol.rst:48-77):
     <out>/out.fasta       one record per distinct haplotype, in order of discovery   cmd.py:183-216
     <out>/snp.fasta       the SNP alleles only                                       cmd.py:218-219
     <out>/gretel.crumbs   "# N n_crumbs n_slices L" + one line per haplotype         cmd.py:224-240
+
+and, with --assign-reads (no reference counterpart; INTEGRATION.md "Read assignment"):
+    <out>/gretel.support  "# n_reads n_informative n_unique n_ambiguous n_unexplained" + one line per haplotype:
+                          i_0, unique, shared, mismatches, unique / n_unique
 """
 from __future__ import annotations
 
@@ -42,8 +46,19 @@ def build_parser():
     p.add_argument("--dumpmatrix", type=str, default=None, help="dump the Hansel tensor (.npz) to this path")
     p.add_argument("--dumpsnps", type=str, default=None, help="dump the SNP positions to this path")
     p.add_argument("--pepper", action="store_true", help="permissive read filter (pysam stepper 'all' in the reference)")
+    add_assign_options(p)
     p.add_argument("--version", action="version", version="%(prog)s " + __version__)
     return p
+
+
+def add_assign_options(p):
+    """--assign-reads and its two settings (shared with gretel_amd.panel)."""
+    p.add_argument("--assign-reads", action="store_true", help="assign every read to the recovered haplotype it matches best and "
+                   "write the read support of each haplotype to gretel.support")
+    p.add_argument("--min-snps", type=int, default=2, help="with --assign-reads: reads with fewer informative SNPs are left "
+                   "out as uninformative [default: 2]")
+    p.add_argument("--max-mismatch", type=int, default=-1, help="with --assign-reads: reads whose best haplotype differs at more "
+                   "SNPs are unexplained (-1 = no limit) [default: -1]")
 
 
 def read_first_fasta_record(path):
@@ -202,8 +217,43 @@ def write_outputs(paths, hansel, vcf_h, args):
                 ",".join("%.2f" % x for x in p["hp_original"]), p["magnitude"]))
 
 
+def support_text(i0s, res):
+    """gretel.support: the totals behind "# ", then per haplotype (in the order of `i0s`, out.fasta's) its i_0, the reads
+    assigned to it alone, the reads it shares a tie with, the mismatches of its unique reads and its share of the unique reads."""
+    lines = ["# %d\t%d\t%d\t%d\t%d\n" % (res["n_reads"], res["n_informative"], res["n_unique"], res["n_ambiguous"],
+                                          res["n_unexplained"])]
+    nu = res["n_unique"]
+    for q, i0 in enumerate(i0s):
+        u = int(res["unique"][q])
+        lines.append("%d\t%d\t%d\t%d\t%.4f\n" % (i0, u, int(res["shared"][q]), int(res["mismatches"][q]), u / nu if nu else 0.0))
+    return "".join(lines)
+
+
+def write_support(paths, hansel, args):
+    """--assign-reads: the distinct haplotypes in out.fasta's order (by i_0) against the support table the fill kept."""
+    import numpy as np
+    keys = sorted(paths, key=lambda x: paths[x]["i_0"])
+    arr = np.array([[s.i for s in paths[k]["hansel_path"]] for k in keys], dtype=np.uint8).reshape(len(keys), hansel.n + 1)
+    res = hansel.assign_reads(arr, min_snps=args.min_snps, max_mismatch=args.max_mismatch)
+    with open(args.out + "/gretel.support", "w") as fh:
+        fh.write(support_text([paths[k]["i_0"] for k in keys], res))
+
+
+def check_assign_options(args):
+    """The refusals of --min-snps / --max-mismatch (before any BAM read or GPU call): a message, or None."""
+    if args.assign_reads and args.min_snps < 1:
+        return "--min-snps must be at least 1"
+    if args.assign_reads and args.max_mismatch < -1:
+        return "--max-mismatch must be -1 (no limit) or at least 0"
+    return None
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    bad = check_assign_options(args)
+    if bad:
+        sys.stderr.write("[FAIL] %s\n" % bad)
+        return 2
     if args.end == -1:
         args.end = util.get_ref_len_from_bam(args.bam, args.contig)               # cmd.py:53-55
         sys.stderr.write("[NOTE] Setting end_pos to %d" % args.end)
@@ -224,7 +274,7 @@ def main(argv=None):
             debug_pos = {int(line.strip()) for line in fh if line.strip()}
     hansel = util.load_from_bam(args.bam, args.contig, args.start, args.end, vcf_h, n_threads=args.threads,
                                 debug_reads=debug_reads, debug_pos=debug_pos, max_depth=args.max_depth,
-                                stepper="all" if args.pepper else "samtools")     # cmd.py:78
+                                stepper="all" if args.pepper else "samtools", keep_reads=args.assign_reads)     # cmd.py:78
     hansel.snapshot_original()                                                    # cmd.py:79 (what the copy is used for)
     if args.dumpmatrix:
         hansel.save_hansel_dump(args.dumpmatrix)                                  # cmd.py:81-82
@@ -243,6 +293,8 @@ def main(argv=None):
     else:
         paths = recover(hansel, vcf_h["N"], args.paths)
     write_outputs(paths, hansel, vcf_h, args)
+    if args.assign_reads:
+        write_support(paths, hansel, args)
     try:                        # the decoder's kept working buffers (include/gretel_io.h: GIO_KEEP_MB): a run has one decode
         from . import bamio
         if getattr(bamio, "_io", None) is not None:

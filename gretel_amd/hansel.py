@@ -83,6 +83,7 @@ class Hansel:
         self._L = 1
         # observations staged on the host until the band width is known (init_matrix gives no hint)
         self._staged = []
+        self.reads = None           # the device support table, kept by fill_from_support(..., keep_reads=True)
         if band is not None:
             self._create(int(band))
 
@@ -277,11 +278,12 @@ class Hansel:
         return g.value
 
     # -- fused fast paths --------------------------------------------------------------------
-    def fill_from_support(self, rank, off, bases, use_end_sentinels=False, reads_handle=None, max_k=None):
+    def fill_from_support(self, rank, off, bases, use_end_sentinels=False, reads_handle=None, max_k=None, keep_reads=False):
         """The pair loop of gretel/util.py:226-286 for a whole support table at once.
         Returns (n_slices, n_crumbs, covered_snps) and sets L like util.py:333.
         max_k: the longest row of the table, where the caller knows it (the native decoder reports it: gio_stats.max_row_len) --
-        a pass over off[] less; gh_reads_upload finds it again on the device and the band is checked against that."""
+        a pass over off[] less; gh_reads_upload finds it again on the device and the band is checked against that.
+        keep_reads: keep the device copy of the table as self.reads (a DeviceReads) for assign_reads; otherwise it is freed."""
         if reads_handle is None:
             reads_handle = DeviceReads(self, rank, off, bases, max_k=max_k)
         else:
@@ -289,7 +291,43 @@ class Hansel:
         st = _lib.gh_fill_stats()
         check(self._lib.gh_fill(self._h, reads_handle._r, int(bool(use_end_sentinels)), C.byref(st)))
         self._L = int(st.L)
+        if keep_reads:
+            self.reads = reads_handle
         return int(st.n_slices), int(st.n_crumbs), int(st.covered_snps)
+
+    def assign_reads(self, paths, reads=None, min_snps=2, max_mismatch=-1, per_read=False):
+        """Which of the haplotypes `paths` (uint8[H][N+1] symbol indices: rows of spin()'s paths) every read of a support table
+        supports (gh_assign_reads; the definition: INTEGRATION.md "Read assignment").  reads: a DeviceReads of this Hansel's
+        window; default self.reads (fill_from_support(..., keep_reads=True)).  Returns a dict: unique, shared, mismatches
+        (int64[H]), n_reads, n_informative, n_unique, n_ambiguous, n_unexplained (ints) and, with per_read, hap, best,
+        informative (int32[n_reads]; hap: the haplotype, -1 uninformative, -2 ambiguous, -3 unexplained).  The tensor is not
+        touched."""
+        if reads is None:
+            reads = getattr(self, "reads", None)
+        if reads is None:
+            raise ValueError("assign_reads needs a support table on the device: pass reads=DeviceReads(...), or fill with "
+                             "fill_from_support(..., keep_reads=True) / util.load_from_bam(..., keep_reads=True)")
+        self._ensure()
+        p = np.ascontiguousarray(paths, dtype=np.uint8)
+        if p.ndim == 1 and p.size == 0:
+            p = p.reshape(0, self.n + 1)
+        if p.ndim != 2 or p.shape[1] != self.n + 1:
+            raise ValueError("paths must be uint8[H][N+1] with N+1 = %d (got shape %s)" % (self.n + 1, p.shape))
+        H = p.shape[0]
+        unique = np.zeros(H, dtype=np.int64)
+        shared = np.zeros(H, dtype=np.int64)
+        mism = np.zeros(H, dtype=np.int64)
+        out = {}
+        if per_read:
+            for k in ("hap", "best", "informative"):
+                out[k] = np.zeros(reads.n_reads, dtype=np.int32)
+        st = _lib.gh_assign_stats()
+        rp = [_p(out[k]) if per_read else None for k in ("hap", "best", "informative")]
+        check(self._lib.gh_assign_reads(self._h, reads._r, _p(p), H, int(min_snps), int(max_mismatch), _p(unique), _p(shared),
+                                        _p(mism), rp[0], rp[1], rp[2], C.byref(st)))
+        out.update(unique=unique, shared=shared, mismatches=mism, n_reads=int(st.n_reads), n_informative=int(st.n_informative),
+                   n_unique=int(st.n_unique), n_ambiguous=int(st.n_ambiguous), n_unexplained=int(st.n_unexplained))
+        return out
 
     def clear(self):
         self._staged = []

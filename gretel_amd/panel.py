@@ -7,7 +7,8 @@ panel (hansel.HanselPanel: the window pipeline over the regions' differing shape
 
     OUT/<name>/out.fasta, OUT/<name>/snp.fasta, OUT/<name>/gretel.crumbs
 
-are byte for byte what `python -m gretel_amd.cmd BAM VCF contig -s start -e end -o OUT/<name>` writes with the same options.
+are byte for byte what `python -m gretel_amd.cmd BAM VCF contig -s start -e end -o OUT/<name>` writes with the same options
+(with --assign-reads also OUT/<name>/gretel.support, one assignment call per region).
 A region gretel cannot recover (a SNP without pairwise evidence, or no read that carries two SNPs) gets gretel's [FAIL] text on
 stderr behind its name and is left out; the exit status is then 1, once every other region has been written.  Stdout: one line
 per recovered region -- name, SNPs, L, paths, distinct haplotypes.  The single-region debugging options (--debughpos,
@@ -38,6 +39,7 @@ def build_parser():
     p.add_argument("--delchar", default="", help="character written for a deletion [default: nothing]")
     p.add_argument("--max-depth", type=int, default=8000, help="read-buffer cap of the pileup, as in gretel_amd.cmd [default: 8000]")
     p.add_argument("--pepper", action="store_true", help="permissive read filter (pysam stepper 'all' in the reference)")
+    cmd.add_assign_options(p)
     p.add_argument("--version", action="version", version="%(prog)s " + __version__)
     return p
 
@@ -60,6 +62,10 @@ def main(argv=None):
     if args.paths < 1:
         sys.stderr.write("[FAIL] -p/--paths must be at least 1\n")
         return 2
+    bad = cmd.check_assign_options(args)
+    if bad:
+        sys.stderr.write("[FAIL] %s\n" % bad)
+        return 2
     util.prefetch_bam(args.bam, regions[0]["contig"], regions[0]["start"], regions[0]["end"])
     vcfs = util.process_vcf_regions(args.vcf, regions)
     stepper = "all" if args.pepper else "samtools"
@@ -69,7 +75,8 @@ def main(argv=None):
         hansel = None
         if vh["N"] > 0:
             try:
-                hansel = util.load_from_bam(args.bam, r["contig"], r["start"], r["end"], vh, max_depth=args.max_depth, stepper=stepper)
+                hansel = util.load_from_bam(args.bam, r["contig"], r["start"], r["end"], vh, max_depth=args.max_depth, stepper=stepper,
+                                             keep_reads=args.assign_reads)
             except ZeroDivisionError:           # no read carries two SNPs (gretel/util.py:333)
                 hansel = None
         if k + 1 < len(regions):                # (the decoder reads the next region while this one is checked)
@@ -97,6 +104,9 @@ def main(argv=None):
                 ns = argparse.Namespace(out=dirn, master=args.master, start=r["start"], end=r["end"], gapchar=args.gapchar,
                                         delchar=args.delchar)
                 cmd.write_outputs(paths, hansel, vh, ns)
+                if args.assign_reads:
+                    ns.min_snps, ns.max_mismatch = args.min_snps, args.max_mismatch
+                    cmd.write_support(paths, hansel, ns)
                 sys.stdout.write("%s\t%d\t%d\t%d\t%d\n" % (r["name"], vh["N"], hansel.L, res["n"], len(paths)))
     try:                        # (the decoder's kept working buffers: see gretel_amd.cmd)
         from . import bamio

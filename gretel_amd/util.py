@@ -398,10 +398,11 @@ def prefetch_bam(bam_path, target_contig, start_pos, end_pos):
 
 def load_from_bam(bam_path, target_contig, start_pos, end_pos, vcf_handler, use_end_sentinels=False,
                   n_threads=1, debug_reads=False, debug_pos=False, stepper="samtools", decoder="native", max_depth=PYSAM_MAX_DEPTH,
-                  **hansel_kw):
+                  keep_reads=False, **hansel_kw):
     """gretel/util.py:33-335.  Returns a device-backed Hansel with n_slices, n_crumbs and L set.
     n_threads is the reference's number of BAM iterator processes (util.py:288-326): the native decoder runs its own
-    threads and the fill is one kernel, so the value changes nothing here -- said once on stderr when it is not 1."""
+    threads and the fill is one kernel, so the value changes nothing here -- said once on stderr when it is not 1.
+    keep_reads: the support table stays on the device as hansel.reads (for Hansel.assign_reads)."""
     if n_threads not in (None, 1):
         sys.stderr.write("[NOTE] -@/--threads %s ignored: the BAM is decoded by libgretel_io.so's own threads and the matrix is filled on the GPU\n" % n_threads)
     native = decoder == "native" and not (debug_reads or debug_pos)
@@ -422,7 +423,7 @@ def load_from_bam(bam_path, target_contig, start_pos, end_pos, vcf_handler, use_
         else:
             max_k = int(np.diff(off).max()) if len(rank) else 0
         hansel = Hansel.init_matrix(SYMBOLS, UNSYMBOLS, vcf_handler["N"], band=max(1, max_k - 1), **hansel_kw)
-        n_slices, n_crumbs, covered = hansel.fill_from_support(rank, off, bases, use_end_sentinels, max_k=max_k)
+        n_slices, n_crumbs, covered = hansel.fill_from_support(rank, off, bases, use_end_sentinels, max_k=max_k, keep_reads=keep_reads)
     sys.stderr.write("[NOTE] Loaded %d breadcrumbs from %d bread slices.\n" % (n_crumbs, n_slices))   # util.py:331
     if n_slices == 0:
         raise ZeroDivisionError("no read carries more than one SNP (gretel/util.py:333 divides by n_reads)")

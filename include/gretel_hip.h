@@ -221,6 +221,29 @@ int gh_panel_create(gh_t **handles, int n, gh_batch_t **out);
 int gh_panel_spin(gh_batch_t *b, int max_paths, double min_remove, uint8_t *paths_out, const int64_t *paths_off,
                   gh_path_rec *recs, int *n_out, int *hole_at);
 
+/* Read assignment (no reference counterpart: Gretel reports haplotypes and likelihoods only; INTEGRATION.md "Read assignment").
+ * Every read of an uploaded support table against n_paths >= 0 haplotypes, paths = [n_paths][N + 1] symbol indices (rows of
+ * gh_spin's paths_out; index 0, the '_' sentinel, is ignored).  Column j of read r lies at SNP rank[r] + j + 1; it is informative
+ * when its symbol is one of A C G T - and the SNP lies in 1..N (N, '_' and columns outside are skipped).  I = informative columns,
+ * m_h = those where paths[h] carries the read's symbol, best = max_h m_h (0 when n_paths = 0), T = {h : m_h = best}.  In this order:
+ * I < min_snps: uninformative (hap -1); max_mismatch >= 0 and I - best > max_mismatch, or n_paths = 0: unexplained (-3);
+ * |T| > 1: ambiguous (-2, shared[h] += 1 for every h in T); else unique (hap = h, unique[h] += 1, mismatches[h] += I - best).
+ * unique / shared / mismatches: [n_paths]; read_hap / read_best / read_informative: [n_reads] each, each may be NULL.
+ * GH_ERR_ARG for n_paths < 0, min_snps < 1, max_mismatch < -1, a path byte above 6, or reads on another device than h;
+ * GH_ERR_SYMBOL when a read holds a byte outside "ACGTN-_".  Reads the table and the paths only: the tensor, L, the fill
+ * statistics and the snapshot stay as they are.  All integers: the results do not depend on the order of the device's atomics. */
+typedef struct {
+    int64_t n_reads;        /* reads in the table */
+    int64_t n_informative;  /* I >= min_snps */
+    int64_t n_unique;
+    int64_t n_ambiguous;
+    int64_t n_unexplained;
+} gh_assign_stats;
+int gh_assign_reads(gh_t *h, const gh_reads_t *reads, const uint8_t *paths, int n_paths, int min_snps, int max_mismatch,
+                    int64_t *unique, int64_t *shared, int64_t *mismatches,
+                    int32_t *read_hap, int32_t *read_best, int32_t *read_informative,
+                    gh_assign_stats *stats);
+
 /* tensor export/import for --dumpmatrix (gretel/cmd.py:81-82) and tests:
  * band layout [(N+2)][band][7][7] as doubles; dense layout [7][7][N+2][N+2] (gretel/cmd.py:76-77). */
 int gh_export_band(gh_t *h, double *out);
