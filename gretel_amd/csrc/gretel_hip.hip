@@ -80,9 +80,30 @@ struct prof_slot {
     bool open = false;            // prof_begin recorded a start event for the launch in flight
 };
 
+// the GH_* switches: a number (def when unset), and "set to 0"
+static int env_int(const char *name, int def)
+{
+    const char *v = getenv(name);
+    return v ? atoi(v) : def;
+}
+static bool env_off(const char *name) { return env_int(name, 1) == 0; }
+
+// GH_WALK (read when a handle is created): see the walker selection further down
+enum { WM_SEG = 0, WM_SPEC = 1, WM_SPEC1 = 2, WM_SRC = 3 };
+
+static int walk_mode_from_env()
+{
+    const char *m = getenv("GH_WALK");
+    if (!m || !*m || !strcmp(m, "seg")) return WM_SEG;
+    if (!strcmp(m, "spec1")) return WM_SPEC1;
+    if (!strcmp(m, "src")) return WM_SRC;
+    return WM_SPEC;
+}
+
+// gh_create value-initialises the handle: what is not given a value here starts at zero / null / false
 struct gh_handle {
     gh_config cfg;
-    int N, W, L;
+    int N, W, L = 1;
     int dev;
     hipStream_t stream;
     size_t n_cells;
@@ -109,7 +130,7 @@ struct gh_handle {
     gh_path_rec *spin_recs;       // [spin_cap]
     int spin_cap;
     int lt_L;
-    bool dirty_marg, dirty_lt, have_orig;
+    bool dirty_marg = true, dirty_lt = true, have_orig;
     const uint8_t *lt_inc_path;   // non-null: the ONLY mutation since G was last built is a path reweight whose fused
                                   // kernel has rewritten the rows it changed (k_lt then only checks the mask flags)
     uint8_t *d_rw_path;           // [N+1] device copy of the path of gh_reweight_path
@@ -126,10 +147,10 @@ struct gh_handle {
     size_t seg_smin_bytes;
     uint8_t *cm5snap;      // [N+2] candidate bits as the last k_seg saw them
     size_t fuse_lds;       // LDS of k_rw's fused prologue for this spin's state space
-    bool band_zero;        // the tensor holds nothing but zeros (gh_create, gh_clear; until something is added): k_fill_own may store instead of add
+    bool band_zero = true; // the tensor holds nothing but zeros (gh_create, gh_clear; until something is added): k_fill_own may store instead of add
     void *tband;           // column conditionals, lane groups of 16 / 32: the band once more, TO-major (tband[bidx(W, p, d, b, a)] = band[bidx(W, p, d, a, b)])
     bool lt_inc_seg;       // lt_inc_path was left by a reweight behind a segment-parallel walk (k_rw / k_rwseg keep the table under every conditional)
-    uint64_t band_epoch, tband_epoch;      // tband mirrors the band iff equal: everything that writes the band counts, k_rw<.., COL> keeps both
+    uint64_t band_epoch = 1, tband_epoch;  // tband mirrors the band iff equal: everything that writes the band counts, k_rw<.., COL> keeps both
     void *seg_halo;        // k_rwseg: per segment, the band blocks of the L positions in front of it (k_emit's copy)
     size_t seg_halo_bytes;
     bool rws;              // inside a gh_spin whose paths run as k_rwseg + k_scan + k_emit (segwalk.hpp)
@@ -154,39 +175,27 @@ struct gh_handle {
     uint8_t *cw_keys_d, *cw_exits_d, *cw_pend_d;      // k_cwalkg: the states as bytes, [S][CW_K][cw_LD] (cw_pend_d: two sets, as the request lists)
     uint8_t *cw_pend_exit_d;                          // ... and the exit states run-on requests arrive with, two sets
     int cw_LD;
-    int cw_rounds;         // walk/scan rounds queued per path (adapts to how often chains stay open)
+    int cw_rounds = 2;     // walk/scan rounds queued per path (adapts to how often chains stay open)
     int cw_stamp;
     int cw_pp;             // k_cwalk launches so far: which of the two request-list sets this launch appends to (cwalk.hpp)
     size_t cw_S;           // segments the pool buffers are sized for (the second set of request lists lies cw_S entries behind the first)
     int64_t cw_stat[4];    // paths through the pools, paths handed to the serial walker, rounds queued, re-queues
-    int force_stale_at;    // GH_SEG_FORCE_STALE=k at creation (tests): path k of every gh_spin finds the table stale once
+    int force_stale_at = env_int("GH_SEG_FORCE_STALE", -1);   // at creation (tests): path k of every gh_spin finds the table stale once
     uint8_t *stage;        // pinned host staging for the results of a spin
     size_t stage_cap;
     double *ew_buf;        // gh_edge_weights_at: seven weights and the candidate mask
     void *asg_buf;         // gh_assign_reads (assign.hpp): counters, paths, match masks and per-read results, grown on demand
     size_t asg_cap;
     bool seg6;             // inside a gh_spin at L = 6 whose table is ranked: every state of every segment (4^6), not pools
-    int cw_round_cap;      // GH_CW_ROUND_CAP=k at creation (tests): never more than k rounds per launch, so that chains stay open and the serial fallback runs
+    int cw_round_cap = env_int("GH_CW_ROUND_CAP", 0);   // =k at creation (tests): never more than k rounds per launch, so that chains stay open and the serial fallback runs
     int spin_partial_stride;   // doubles between two paths' partial sums of the removed mass in a spin (0 outside spins)
     int spin_requeues;     // how often the last gh_spin rebuilt the table and queued the remaining paths again
-    gh_fill_stats stats;
-    int wmode;                    // WM_*: which path extension (GH_WALK at creation)
-    bool lt_full;                 // GH_LT_FULL=1 at creation: rebuild the conditional table in full before every path (A/B)
+    gh_fill_stats stats = {0, 0, 0, 1, 0};
+    int wmode = walk_mode_from_env();        // WM_*: which path extension (GH_WALK at creation)
+    bool lt_full = env_int("GH_LT_FULL", 0) != 0;   // at creation: rebuild the conditional table in full before every path (A/B)
     int prof;                     // 0 = off, k = bracket every k-th launch of each kernel
     prof_slot ps[GH_K_COUNT];
 };
-
-// GH_WALK (read when a handle is created): see the walker selection further down
-enum { WM_SEG = 0, WM_SPEC = 1, WM_SPEC1 = 2, WM_SRC = 3 };
-
-static int walk_mode_from_env()
-{
-    const char *m = getenv("GH_WALK");
-    if (!m || !*m || !strcmp(m, "seg")) return WM_SEG;
-    if (!strcmp(m, "spec1")) return WM_SPEC1;
-    if (!strcmp(m, "src")) return WM_SRC;
-    return WM_SPEC;
-}
 
 struct gh_reads {
     int dev;
@@ -206,6 +215,113 @@ struct gh_reads {
 
 static inline size_t esize(const gh_handle *h) { return h->cfg.storage == GH_STORAGE_F64 ? 8 : 4; }
 
+// f(T()) with T = the handle's storage type (float / double): one launch site per kernel, instantiated for both
+template <typename F> static auto with_storage(const gh_handle *h, F &&f)
+{
+    return h->cfg.storage == GH_STORAGE_F64 ? f(0.0) : f(0.0f);
+}
+
+// raises kernel K's dynamic-LDS limit where this device's last raise was lower: once per instantiation and device, not on
+// every launch (gh_batch_spin runs gh_spin on several host threads)
+template <auto K> static void lds_limit(size_t lds, int dev)
+{
+    static std::atomic<size_t> set[64];
+    if (lds > set[dev & 63]) {
+        hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        set[dev & 63] = lds;
+    }
+}
+
+// the window's control words to the host: one copy, one wait on its stream
+static int read_state(gh_handle *h, dev_state *hs)
+{
+    hipError_t e = hipMemcpyAsync(hs, h->dstate, sizeof *hs, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail(GH_ERR_HIP, "gh_spin failed: %s", hipGetErrorString(e));
+    return GH_OK;
+}
+
+// algorithmic bytes (gh_profile_bytes, gh_batch_profile_get; bench.py's roofline), es = bytes per element.  The extension of a
+// path, SURVEY 8(d): per step the marginal cell + L history cells (49 elements each) + the original marginals (7 x 4 B).  What
+// this build's layout needs per step is one table row: N * (L * 40 + 25) bytes.
+static double walk_bytes(int N, int L, double es) { return (double)N * ((1.0 + (double)L) * CELL * es + 28.0); }
+// the reweight of a path: the reweighted elements (read+write) + the marginal pass (read cell (p,p+1), write the tables)
+// (+ rows: one band row read and L x 5 table entries written per (source, lag) when the table rows are rewritten too)
+static double reweight_bytes(int N, int W, int L, double es, bool rows)
+{
+    const int wl = W < L ? W : L;
+    return (double)(N + 1) * ((double)W * 2.0 * es + 1.0 + CELL * es + 2 * 64 + 88 + 8) +
+           (rows ? (double)N * ((double)wl * 7 * es + (double)L * LT_ROW * 8.0) : 0.0);
+}
+
+// k_marg's and k_lt's arguments by name (kernels.hpp takes them in this order); what a launch leaves out is null / 0
+struct marg_args {
+    void *band = nullptr;
+    int N = 0, W = 0;
+    double *cnt = nullptr, *marg = nullptr;
+    int32_t *nvalid = nullptr;
+    uint32_t *cmask = nullptr;
+    double *minfo = nullptr;
+    dev_state *st = nullptr;
+    const win_desc *wd = nullptr;
+    const uint8_t *rw_path = nullptr;
+    double ratio = 0.0;
+    int use_state_ratio = 0;
+    double *partial = nullptr;
+    int spin = 0;
+    double *G = nullptr;            // the batched k_marg<T,true>: any non-null pointer = take G from the descriptor
+    int L = 0, cond_mode = 0;
+    const double *segmin = nullptr;
+    gh_path_rec *seg_rec = nullptr;
+    symmap sm{};
+    int offer_zero = 0;
+    double *rinfo = nullptr;
+};
+template <bool RW> static void launch_marg(const gh_handle *h, dim3 grid, hipStream_t st, const marg_args &a)
+{
+    with_storage(h, [&](auto z) {
+        using T = decltype(z);
+        hipLaunchKernelGGL((k_marg<T, RW>), grid, dim3(256), 0, st, (T *)a.band, a.N, a.W, a.cnt, a.marg, a.nvalid, a.cmask, a.minfo,
+                           a.st, a.wd, a.rw_path, a.ratio, a.use_state_ratio, a.partial, a.spin, a.G, a.L, a.cond_mode, a.segmin,
+                           a.seg_rec, a.sm, a.offer_zero, a.rinfo);
+    });
+}
+
+// the handle's own tensors and tables (single-window launches)
+static marg_args marg_of(const gh_handle *h)
+{
+    marg_args a;
+    a.band = h->band; a.N = h->N; a.W = h->W; a.cnt = h->cnt; a.marg = h->marg; a.nvalid = h->nvalid; a.cmask = h->cmask;
+    a.minfo = h->minfo; a.st = h->dstate; a.sm = h->sm; a.offer_zero = h->cfg.offer_zero; a.rinfo = h->need_rinfo ? h->rinfo : nullptr;
+    return a;
+}
+
+struct lt_args {
+    const void *band = nullptr;
+    int N = 0, W = 0, L = 0, cond_mode = 0;
+    int bake_lm = 0;                // (k_lt's marginal_term)
+    const double *cnt = nullptr;
+    const int32_t *nvalid = nullptr;
+    const uint32_t *cmask = nullptr;
+    const double *minfo = nullptr;
+    double *G = nullptr;
+    dev_state *st = nullptr;
+    const uint8_t *inc_path = nullptr;
+    const win_desc *wd = nullptr;
+    int spin = 0, allow_ranked = 0;
+    double *Ht = nullptr, *Yt = nullptr;
+    symmap sm{};
+    const void *tband = nullptr;
+};
+static void launch_lt(const gh_handle *h, dim3 grid, hipStream_t st, const lt_args &a)
+{
+    with_storage(h, [&](auto z) {
+        using T = decltype(z);
+        hipLaunchKernelGGL(k_lt<T>, grid, dim3(256), 0, st, (const T *)a.band, a.N, a.W, a.L, a.cond_mode, a.bake_lm, a.cnt, a.nvalid,
+                           a.cmask, a.minfo, a.G, a.st, a.inc_path, a.wd, a.spin, a.allow_ranked, a.Ht, a.Yt, a.sm, (const T *)a.tband);
+    });
+}
+
 static int set_dev(const gh_handle *h)
 {
     HIPCHK(hipSetDevice(h->dev));
@@ -215,7 +331,7 @@ static int set_dev(const gh_handle *h)
 // launch check: GH_DEBUG_SYNC=1 synchronises after every launch so that a fault names its kernel
 static int post_launch(gh_handle *h, const char *what)
 {
-    static const bool dbg = getenv("GH_DEBUG_SYNC") && atoi(getenv("GH_DEBUG_SYNC"));
+    static const bool dbg = env_int("GH_DEBUG_SYNC", 0) != 0;
     hipError_t e = hipGetLastError();
     if (e == hipSuccess && dbg) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) return fail(GH_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
@@ -392,40 +508,11 @@ extern "C" int gh_create(const gh_config *cfg, gh_t **out)
     memset(h->cfg.cand_order, 0, sizeof h->cfg.cand_order);
     memcpy(h->cfg.cand_order, order, 5);
     h->sm = make_symmap(order);
-    h->rinfo = nullptr; h->pipe_pk = nullptr; h->pipe_gp = nullptr; h->pipe_gp_bytes = 0; h->pipe_lm = nullptr; h->pipe_gw = nullptr; h->pipe_gw_bytes = 0; h->lt_baked = false; h->ht_stale = false;
-    h->need_rinfo = cfg->marginal_term != 0 || (getenv("GH_FUSE") && atoi(getenv("GH_FUSE")) >= 1);
+    h->need_rinfo = cfg->marginal_term != 0 || env_int("GH_FUSE", 0) >= 1;
     h->dev = dev;
     h->N = cfg->n_snps;
     h->W = cfg->band;
-    h->L = 1;
     h->n_cells = (size_t)(h->N + 2) * h->W;
-    h->lt = nullptr; h->ht = nullptr; h->yt = nullptr; h->lt_L = 0;
-    h->spin_paths = nullptr; h->spin_recs = nullptr; h->spin_cap = 0;
-    h->seg_hist = nullptr; h->seg_maps = nullptr; h->seg_pmaps = nullptr; h->seg_gmaps = nullptr; h->seg_min = nullptr; h->lmsel1 = nullptr;
-    h->seg_smin = nullptr; h->seg_gmin = nullptr; h->cm5snap = nullptr; h->fuse = false; h->seg_smin_bytes = 0;
-    h->seg_halo = nullptr; h->seg_halo_bytes = 0; h->rws = false;
-    h->spin_lmsel = nullptr; h->seg_L = 0; h->spin_requeues = 0; h->spin_partial_stride = 0;
-    h->cw_keys = nullptr; h->cw_exits = nullptr; h->cw_hist = nullptr; h->cw_last_hit = nullptr; h->cw_npool = nullptr;
-    h->cw_pend_exit = nullptr; h->cw_pend_ready = nullptr; h->cw_phist = nullptr;
-    h->cw_walked = nullptr; h->cw_nxt = nullptr; h->cw_true = nullptr; h->cw_pend = nullptr; h->cw_npend = nullptr; h->cw_ready = false; h->cw_off = false; h->cw_wide = false; h->cw_pool_wide = false; h->cw_rounds = 2; h->cw_stamp = 0; h->cw_pp = 0; h->cw_S = 0;
-    h->cw_keys_d = nullptr; h->cw_exits_d = nullptr; h->cw_pend_d = nullptr; h->cw_pend_exit_d = nullptr; h->cw_LD = 0; h->cw_no_rw = false;
-    memset(h->cw_stat, 0, sizeof h->cw_stat);
-    h->force_stale_at = getenv("GH_SEG_FORCE_STALE") ? atoi(getenv("GH_SEG_FORCE_STALE")) : -1;
-    h->cw_round_cap = getenv("GH_CW_ROUND_CAP") ? atoi(getenv("GH_CW_ROUND_CAP")) : 0;
-    h->stage = nullptr; h->stage_cap = 0;
-    h->seg6 = false;
-    h->ew_buf = nullptr;
-    memset(h->fill_seen, 0, sizeof h->fill_seen);
-    h->dirty_marg = h->dirty_lt = true; h->lt_inc_path = nullptr; h->band_zero = true;      // (the allocation is zeroed below / above: gh_create)
-    h->tband = nullptr; h->band_epoch = 1; h->tband_epoch = 0; h->lt_inc_seg = false;
-    h->have_orig = false;
-    h->lt_inc_path = nullptr; h->d_rw_path = nullptr;
-    h->prof = 0;
-    h->wmode = walk_mode_from_env();
-    h->lt_full = getenv("GH_LT_FULL") && atoi(getenv("GH_LT_FULL"));
-    h->partial = nullptr; h->partial_cap = 0;
-    memset(&h->stats, 0, sizeof h->stats);
-    h->stats.L = 1;
     const size_t np = (size_t)h->N + 2;
 #define ALLOC(ptr, bytes)                                                                     \
     do {                                                                                      \
@@ -683,7 +770,7 @@ extern "C" int gh_fill(gh_t *h, const gh_reads_t *r, int use_end_sentinels, gh_f
         const double bytes = 8.0 * 0 + (double)r->n_reads * 12.0 + (double)r->n_bases;   // + 8*adds, added below
         prof_begin(h, GH_K_FILL);
         // sorted tables: LDS-privatised counting when a run of reads stays inside a slice that fits in LDS
-        static const bool no_sorted = getenv("GH_FILL_SCATTER") && atoi(getenv("GH_FILL_SCATTER"));
+        static const bool no_sorted = env_int("GH_FILL_SCATTER", 0) != 0;
         const int rpb = FILL_RPB;                                 // reads per workgroup
         int max_pos = 0;
         if (r->sorted && !no_sorted) {
@@ -699,63 +786,52 @@ extern "C" int gh_fill(gh_t *h, const gh_reads_t *r, int use_end_sentinels, gh_f
         // may see 65 536 reads).  GH_FILL_OWN=0 keeps the older fills (the tests run them against each other).
         int own_P = 0;
         bool own_half = true;
-        if (r->sorted && r->first_at && !no_sorted && !(getenv("GH_FILL_OWN") && atoi(getenv("GH_FILL_OWN")) == 0)) {
+        if (r->sorted && r->first_at && !no_sorted && !env_off("GH_FILL_OWN")) {
             int P = (h->N + 2 + 1023) / 1024;                    // about a thousand workgroups ...
             if (P < 2 * r->max_k) P = 2 * r->max_k;              // ... that visit a read 1.5 times at most
             if (P < 8) P = 8;
             // the reads one workgroup can see: ranks within P + max_k positions
             const int64_t win = (int64_t)((P + r->max_k + 127) / 128 + 1) * r->dens128;
-            own_half = win < 65536 && !(getenv("GH_FILL_OWN_WIDE") && atoi(getenv("GH_FILL_OWN_WIDE")));      // (the tests force the 4-byte counters)
+            own_half = win < 65536 && !env_int("GH_FILL_OWN_WIDE", 0);      // (the tests force the 4-byte counters)
             const size_t per_pos = (size_t)h->W * CELL * (own_half ? 2 : 4);
             const int P_lds = (int)((150 * 1024 - FILL_OWN_SYMS) / per_pos);
             if (P > P_lds) P = P_lds;
             if (P >= r->max_k && P >= 8 && r->max_k <= FILL_OWN_SYMS) own_P = P;               // (narrower: every read would be visited by many workgroups)
         }
-        if (own_P > 0) {
-            const unsigned gb = (unsigned)((h->N + 2 + own_P - 1) / own_P);
-            const size_t sym_off = (((size_t)own_P * h->W * CELL * (own_half ? 2 : 4)) + 15) & ~(size_t)15;
-            const size_t lds = sym_off + FILL_OWN_SYMS;
-#define FILL_OWN(T_, CT_, Z_, G_) do {                                                                                                   \
-                hipFuncSetAttribute((const void *)k_fill_own<T_, CT_, Z_, G_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);       \
-                hipLaunchKernelGGL((k_fill_own<T_, CT_, Z_, G_>), dim3(gb), dim3(1024), lds, h->stream, (T_ *)h->band, h->N, h->W, r->rank,  \
-                                   r->off, r->bases, r->n_reads, own_P, r->max_k, use_end_sentinels, h->dstate, r->first_at, r->n_first, (int)sym_off); \
-            } while (0)
-            // lanes per read: one for short reads, four / eight for long ones (a lane takes every G-th from-index of its read)
-#define FILL_OWN_G(T_, CT_, Z_) do { if (r->max_k <= 8) FILL_OWN(T_, CT_, Z_, 1); else if (r->max_k <= 32) FILL_OWN(T_, CT_, Z_, 4); else FILL_OWN(T_, CT_, Z_, 8); } while (0)
-#define FILL_OWN_Z(T_, CT_) do { if (h->band_zero) FILL_OWN_G(T_, CT_, true); else FILL_OWN_G(T_, CT_, false); } while (0)
-            if (h->cfg.storage == GH_STORAGE_F64) { if (own_half) FILL_OWN_Z(double, uint16_t); else FILL_OWN_Z(double, uint32_t); }
-            else { if (own_half) FILL_OWN_Z(float, uint16_t); else FILL_OWN_Z(float, uint32_t); }
+        with_storage(h, [&](auto z) {
+            using T = decltype(z);
+            if (own_P > 0) {
+                const unsigned gb = (unsigned)((h->N + 2 + own_P - 1) / own_P);
+                const size_t sym_off = (((size_t)own_P * h->W * CELL * (own_half ? 2 : 4)) + 15) & ~(size_t)15;
+                const size_t lds = sym_off + FILL_OWN_SYMS;
+#define FILL_OWN(CT_, Z_, G_) do {                                                                                                       \
+                    lds_limit<k_fill_own<T, CT_, Z_, G_>>(lds, h->dev);                                                                  \
+                    hipLaunchKernelGGL((k_fill_own<T, CT_, Z_, G_>), dim3(gb), dim3(1024), lds, h->stream, (T *)h->band, h->N, h->W, r->rank, \
+                                       r->off, r->bases, r->n_reads, own_P, r->max_k, use_end_sentinels, h->dstate, r->first_at, r->n_first, (int)sym_off); \
+                } while (0)
+                // lanes per read: one for short reads, four / eight for long ones (a lane takes every G-th from-index of its read)
+#define FILL_OWN_G(CT_, Z_) do { if (r->max_k <= 8) FILL_OWN(CT_, Z_, 1); else if (r->max_k <= 32) FILL_OWN(CT_, Z_, 4); else FILL_OWN(CT_, Z_, 8); } while (0)
+#define FILL_OWN_Z(CT_) do { if (h->band_zero) FILL_OWN_G(CT_, true); else FILL_OWN_G(CT_, false); } while (0)
+                if (own_half) FILL_OWN_Z(uint16_t); else FILL_OWN_Z(uint32_t);
 #undef FILL_OWN_G
 #undef FILL_OWN_Z
 #undef FILL_OWN
-        } else if (max_pos >= r->max_k + 8) {
-            const unsigned gb = (unsigned)((r->n_reads + rpb - 1) / rpb);
-            const size_t lds = (size_t)max_pos * h->W * CELL * sizeof(unsigned);
-            if (h->cfg.storage == GH_STORAGE_F64) {
-                hipFuncSetAttribute((const void *)k_fill_sorted<double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                hipLaunchKernelGGL(k_fill_sorted<double>, dim3(gb), dim3(block), lds, h->stream, (double *)h->band, h->N, h->W,
+            } else if (max_pos >= r->max_k + 8) {
+                const unsigned gb = (unsigned)((r->n_reads + rpb - 1) / rpb);
+                const size_t lds = (size_t)max_pos * h->W * CELL * sizeof(unsigned);
+                lds_limit<k_fill_sorted<T>>(lds, h->dev);
+                hipLaunchKernelGGL(k_fill_sorted<T>, dim3(gb), dim3(block), lds, h->stream, (T *)h->band, h->N, h->W,
                                    r->rank, r->off, r->bases, r->n_reads, rpb, max_pos, r->max_k, use_end_sentinels, h->dstate);
-            } else {
-                hipFuncSetAttribute((const void *)k_fill_sorted<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                hipLaunchKernelGGL(k_fill_sorted<float>, dim3(gb), dim3(block), lds, h->stream, (float *)h->band, h->N, h->W,
-                                   r->rank, r->off, r->bases, r->n_reads, rpb, max_pos, r->max_k, use_end_sentinels, h->dstate);
-            }
-        } else if (r->max_k >= FILL_PAIRS_MIN_K && r->max_k <= 32 && !(getenv("GH_FILL_PAIRS") && atoi(getenv("GH_FILL_PAIRS")) == 0)) {
-            // long reads, sparse tensor: 32 lanes per read (k_fill_pairs)
-            int64_t nbp = (r->n_reads * 32 + block - 1) / block;
-            if (nbp > 256 * 64) nbp = 256 * 64;
-            if (h->cfg.storage == GH_STORAGE_F64)
-                hipLaunchKernelGGL(k_fill_pairs<double>, dim3((unsigned)nbp), dim3(block), 0, h->stream, (double *)h->band,
+            } else if (r->max_k >= FILL_PAIRS_MIN_K && r->max_k <= 32 && !env_off("GH_FILL_PAIRS")) {
+                // long reads, sparse tensor: 32 lanes per read (k_fill_pairs)
+                int64_t nbp = (r->n_reads * 32 + block - 1) / block;
+                if (nbp > 256 * 64) nbp = 256 * 64;
+                hipLaunchKernelGGL(k_fill_pairs<T>, dim3((unsigned)nbp), dim3(block), 0, h->stream, (T *)h->band,
                                    h->N, h->W, r->rank, r->off, r->bases, r->n_reads, use_end_sentinels, h->dstate);
-            else
-                hipLaunchKernelGGL(k_fill_pairs<float>, dim3((unsigned)nbp), dim3(block), 0, h->stream, (float *)h->band,
+            } else
+                hipLaunchKernelGGL(k_fill<T>, dim3((unsigned)nb), dim3(block), 0, h->stream, (T *)h->band,
                                    h->N, h->W, r->rank, r->off, r->bases, r->n_reads, use_end_sentinels, h->dstate);
-        } else if (h->cfg.storage == GH_STORAGE_F64)
-            hipLaunchKernelGGL(k_fill<double>, dim3((unsigned)nb), dim3(block), 0, h->stream, (double *)h->band,
-                               h->N, h->W, r->rank, r->off, r->bases, r->n_reads, use_end_sentinels, h->dstate);
-        else
-            hipLaunchKernelGGL(k_fill<float>, dim3((unsigned)nb), dim3(block), 0, h->stream, (float *)h->band,
-                               h->N, h->W, r->rank, r->off, r->bases, r->n_reads, use_end_sentinels, h->dstate);
+        });
         prof_end(h, GH_K_FILL, bytes);
         { int rc_ = post_launch(h, "k_fill"); if (rc_) return rc_; }
     }
@@ -794,16 +870,13 @@ extern "C" int gh_get(gh_t *h, int a, int b, int i, int j, double *out)
     int rc = cell_index(h, a, b, i, j, &idx);
     if (rc < 0) return rc;
     if (rc == 1) { *out = 0.0; return GH_OK; }
-    if (h->cfg.storage == GH_STORAGE_F64) {
-        HIPCHK(hipMemcpyAsync(out, (double *)h->band + idx, 8, hipMemcpyDeviceToHost, h->stream));
+    return with_storage(h, [&](auto z) -> int {
+        using T = decltype(z);
+        HIPCHK(hipMemcpyAsync(&z, (T *)h->band + idx, sizeof z, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
-    } else {
-        float f;
-        HIPCHK(hipMemcpyAsync(&f, (float *)h->band + idx, 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        *out = (double)f;
-    }
-    return GH_OK;
+        *out = (double)z;
+        return GH_OK;
+    });
 }
 
 extern "C" int gh_add_batch(gh_t *h, const uint8_t *a, const uint8_t *b, const int32_t *i, const int32_t *j, int64_t n)
@@ -826,10 +899,10 @@ extern "C" int gh_add_batch(gh_t *h, const uint8_t *a, const uint8_t *b, const i
     if (rc == GH_OK) {
         const int block = 256;
         const unsigned nb = (unsigned)((n + block - 1) / block);
-        if (h->cfg.storage == GH_STORAGE_F64)
-            hipLaunchKernelGGL(k_add_batch<double>, dim3(nb), dim3(block), 0, h->stream, (double *)h->band, h->N, h->W, da, db, di, dj, n, h->dstate);
-        else
-            hipLaunchKernelGGL(k_add_batch<float>, dim3(nb), dim3(block), 0, h->stream, (float *)h->band, h->N, h->W, da, db, di, dj, n, h->dstate);
+        with_storage(h, [&](auto z) {
+            using T = decltype(z);
+            hipLaunchKernelGGL(k_add_batch<T>, dim3(nb), dim3(block), 0, h->stream, (T *)h->band, h->N, h->W, da, db, di, dj, n, h->dstate);
+        });
         h->dirty_marg = h->dirty_lt = true; h->lt_inc_path = nullptr; h->band_zero = false; h->band_epoch++;
         int64_t s0 = h->stats.n_slices, c0 = h->stats.n_crumbs, v0 = h->stats.covered_snps;
         rc = pull_fill_state(h, "gh_add_batch");
@@ -857,10 +930,10 @@ extern "C" int gh_reweight_obs(gh_t *h, int a, int b, int i, int j, double ratio
     double rem = 0.0;
     if (rc == 0) {
         double *d_rem = &h->d_rec->magnitude;
-        if (h->cfg.storage == GH_STORAGE_F64)
-            hipLaunchKernelGGL(k_reweight_one<double>, dim3(1), dim3(1), 0, h->stream, (double *)h->band + idx, ratio, d_rem);
-        else
-            hipLaunchKernelGGL(k_reweight_one<float>, dim3(1), dim3(1), 0, h->stream, (float *)h->band + idx, ratio, d_rem);
+        with_storage(h, [&](auto z) {
+            using T = decltype(z);
+            hipLaunchKernelGGL(k_reweight_one<T>, dim3(1), dim3(1), 0, h->stream, (T *)h->band + idx, ratio, d_rem);
+        });
         HIPCHK(hipMemcpyAsync(&rem, d_rem, 8, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
         h->dirty_marg = h->dirty_lt = true; h->lt_inc_path = nullptr; h->band_epoch++;
@@ -878,16 +951,7 @@ static int ensure_marg(gh_handle *h)
     // re-arm the "first SNP without a candidate" word that k_marg min-reduces into
     HIPCHK(hipMemsetAsync(&h->dstate->first_hole, 0x7f, 4 * sizeof(int), h->stream));   // first_hole, nodel, cm_same, narrow
     prof_begin(h, GH_K_MARG);
-    if (h->cfg.storage == GH_STORAGE_F64)
-        hipLaunchKernelGGL((k_marg<double, false>), dim3((threads + block - 1) / block), dim3(block), 0, h->stream,
-                           (double *)h->band, h->N, h->W, h->cnt, h->marg, h->nvalid, h->cmask, h->minfo, h->dstate, (const win_desc *)nullptr,
-                           (const uint8_t *)nullptr, 0.0, 0, (double *)nullptr, 0, (double *)nullptr, 0, 0, (const double *)nullptr, (gh_path_rec *)nullptr,
-                           h->sm, h->cfg.offer_zero, h->need_rinfo ? h->rinfo : (double *)nullptr);
-    else
-        hipLaunchKernelGGL((k_marg<float, false>), dim3((threads + block - 1) / block), dim3(block), 0, h->stream,
-                           (float *)h->band, h->N, h->W, h->cnt, h->marg, h->nvalid, h->cmask, h->minfo, h->dstate, (const win_desc *)nullptr,
-                           (const uint8_t *)nullptr, 0.0, 0, (double *)nullptr, 0, (double *)nullptr, 0, 0, (const double *)nullptr, (gh_path_rec *)nullptr,
-                           h->sm, h->cfg.offer_zero, h->need_rinfo ? h->rinfo : (double *)nullptr);
+    launch_marg<false>(h, dim3((threads + block - 1) / block), h->stream, marg_of(h));
     // algorithmic bytes: read the (p,p+1) cell, write cnt/marg (2x64), minfo (88), nvalid+cmask (8)
     prof_end(h, GH_K_MARG, (double)(h->N + 1) * (CELL * esize(h) + 2 * 64 + 88 + 8));
     { int rc_ = post_launch(h, "k_marg"); if (rc_) return rc_; }
@@ -918,7 +982,7 @@ static bool seg_ok(int wm, int L);
 // k_seg / k_scan / k_rw carry the minima over the enumerated states
 static bool mixed_allowed(const gh_handle *h)
 {
-    static const bool off = getenv("GH_MIXED") && atoi(getenv("GH_MIXED")) == 0;
+    static const bool off = env_off("GH_MIXED");
     return !off && !h->fuse && h->L == SEGM_L && h->wmode == WM_SEG && !h->cfg.offer_zero;
 }
 
@@ -944,17 +1008,13 @@ static int ensure_lt(gh_handle *h, bool baked = false, bool derived = true)
     if (nb > 256 * 16) nb = 256 * 16;
     // (column conditionals: the to-major copy, while it mirrors the band, makes the column sums contiguous reads)
     const void *tb_lt = (h->tband && h->tband_epoch == h->band_epoch) ? h->tband : nullptr;
+    lt_args a;
+    a.band = h->band; a.N = h->N; a.W = h->W; a.L = h->L; a.cond_mode = h->cfg.cond_mode; a.bake_lm = want_baked ? 1 : 0;
+    a.cnt = h->cnt; a.nvalid = h->nvalid; a.cmask = h->cmask; a.minfo = h->minfo; a.G = h->lt; a.st = h->dstate; a.inc_path = inc;
+    a.allow_ranked = walk_ranked_ok(h->wmode, h->L);
+    a.Ht = derived ? h->ht : nullptr; a.Yt = derived ? h->yt : nullptr; a.sm = h->sm; a.tband = tb_lt;
     prof_begin(h, GH_K_LT);
-    if (h->cfg.storage == GH_STORAGE_F64)
-        hipLaunchKernelGGL(k_lt<double>, dim3((unsigned)nb), dim3(block), 0, h->stream, (const double *)h->band,
-                           h->N, h->W, h->L, h->cfg.cond_mode, want_baked ? 1 : 0, h->cnt, h->nvalid, h->cmask,
-                           h->minfo, h->lt, h->dstate, inc, (const win_desc *)nullptr, 0, walk_ranked_ok(h->wmode, h->L),
-                           derived ? h->ht : (double *)nullptr, derived ? h->yt : (double *)nullptr, h->sm, (const double *)tb_lt);
-    else
-        hipLaunchKernelGGL(k_lt<float>, dim3((unsigned)nb), dim3(block), 0, h->stream, (const float *)h->band,
-                           h->N, h->W, h->L, h->cfg.cond_mode, want_baked ? 1 : 0, h->cnt, h->nvalid, h->cmask,
-                           h->minfo, h->lt, h->dstate, inc, (const win_desc *)nullptr, 0, walk_ranked_ok(h->wmode, h->L),
-                           derived ? h->ht : (double *)nullptr, derived ? h->yt : (double *)nullptr, h->sm, (const float *)tb_lt);
+    launch_lt(h, dim3((unsigned)nb), h->stream, a);
     const int wl = h->W < h->L ? h->W : h->L;
     // algorithmic bytes: full = read the band cells within reach + write G; after a fused reweight = the two flags
     prof_end(h, GH_K_LT, inc ? 8.0
@@ -1018,14 +1078,11 @@ extern "C" int gh_edge_weights_at(gh_t *h, int p, const uint8_t *path, double w[
     double *d_w = h->ew_buf;
     hipError_t e = hipMemcpyAsync(d_hist, hist.data(), lmax, hipMemcpyHostToDevice, h->stream);
     if (e != hipSuccess) return fail(GH_ERR_HIP, "gh_edge_weights_at failed: %s", hipGetErrorString(e));
-    if (h->cfg.storage == GH_STORAGE_F64)
-        hipLaunchKernelGGL(k_edge_weights<double>, dim3(1), dim3(64), 0, h->stream, (const double *)h->band, h->W,
-                           h->cfg.cond_mode, p, h->L, h->cfg.marginal_term, h->cnt, h->marg, h->nvalid, h->cmask,
-                           d_hist, d_w, (int *)(d_w + 7));
-    else
-        hipLaunchKernelGGL(k_edge_weights<float>, dim3(1), dim3(64), 0, h->stream, (const float *)h->band, h->W,
-                           h->cfg.cond_mode, p, h->L, h->cfg.marginal_term, h->cnt, h->marg, h->nvalid, h->cmask,
-                           d_hist, d_w, (int *)(d_w + 7));
+    with_storage(h, [&](auto z) {
+        using T = decltype(z);
+        hipLaunchKernelGGL(k_edge_weights<T>, dim3(1), dim3(64), 0, h->stream, (const T *)h->band, h->W, h->cfg.cond_mode, p, h->L,
+                           h->cfg.marginal_term, h->cnt, h->marg, h->nvalid, h->cmask, d_hist, d_w, (int *)(d_w + 7));
+    });
     double hw[8];
     e = hipMemcpyAsync(hw, d_w, sizeof hw, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
@@ -1101,7 +1158,7 @@ static int alloc_lt(gh_handle *h)
 // path extension / reweight -------------------------------------------------------------------
 static int walk_threads()
 {
-    static const int n = getenv("GH_WALK_THREADS") ? atoi(getenv("GH_WALK_THREADS")) : 512;
+    static const int n = env_int("GH_WALK_THREADS", 512);
     return (n >= 192 && n <= 512 && n % 64 == 0) ? n : 512;
 }
 #define WALK_THREADS walk_threads()
@@ -1128,7 +1185,7 @@ static bool cw_digit_mode(const gh_handle *h) { return h->cw_wide ? h->L > CW_MA
 // k_cwalk) instead of k_cwalkg (GH_CWALK2=0: k_cwalkg, for the tests and A/B; read per launch)
 static bool cw2_ok(const gh_handle *h)
 {
-    if (getenv("GH_CWALK2") && atoi(getenv("GH_CWALK2")) == 0) return false;
+    if (env_off("GH_CWALK2")) return false;
     return h->cw_wide ? (h->L > CW_MAX_L5 && h->L <= CW2_MAX_L5) : (h->L > CW_MAX_L && h->L <= CW2_MAX_L);
 }
 
@@ -1220,6 +1277,21 @@ static int alloc_seg(gh_handle *h)
     return GH_OK;
 }
 
+// the segment-parallel walk's parameters for this handle (k_seg_fin reads N, L, st and segmin only)
+static seg_params seg_make_params(const gh_handle *h, int rearm, int check_masks, uint8_t *d_path, double *d_lmsel)
+{
+    seg_params P;
+    memset(&P, 0, sizeof P);
+    P.N = h->N; P.L = h->L; P.rearm = rearm; P.check_masks = check_masks;
+    P.G = h->lt; P.minfo = h->minfo; P.rinfo = h->rinfo; P.mt = h->cfg.marginal_term; P.nanp = h->cfg.marginal_term && h->cfg.offer_zero; P.sm = h->sm; P.st = h->dstate;
+    P.hist = h->seg_hist; P.maps = h->seg_maps; P.pmaps = h->seg_pmaps; P.gmaps = h->seg_gmaps; P.segmin = h->seg_min;
+    P.smin = h->seg_smin; P.gmin = h->seg_gmin; P.cm5snap = h->cm5snap;
+    P.W = h->W; P.esz = (int)esize(h); P.band = h->band;
+    P.rwflags = reinterpret_cast<int2 *>(h->seg_min + CW_MAX_SEG);
+    P.path_out = d_path; P.lmsel = d_lmsel;
+    return P;
+}
+
 template <int LC>
 static void launch_seg_lc(gh_handle *h, const seg_params &P)
 {
@@ -1228,33 +1300,29 @@ static void launch_seg_lc(gh_handle *h, const seg_params &P)
     const size_t lds_seg = max_cls(LC, [&](int R) { return seg_lds_total(R, LC); });
     const size_t lds_scan = max_cls(LC, [&](int R) { return scan_lds_bytes(N, LC, R); });
     const size_t lds_emit = max_cls(LC, [&](int R) { return emit_lds_bytes(N, LC, R); });
-    // per instantiation and device: raise the dynamic-LDS limit once, not on every launch
-    static std::atomic<size_t> set_seg[64], set_scan[64], set_emit[64], set_segt[64], set_scant[64];      // (gh_batch_spin runs gh_spin on several host threads)
-    const int dv = dev & 63;
     const int S = (int)max_cls(LC, [&](int R) { return (size_t)seg_geometry(N, LC, R).S; }), G1 = (int)max_cls(LC, [&](int R) { return (size_t)seg_geometry(N, LC, R).G1; });
     if (h->fuse) {
         // spins without k_emit: k_seg / k_scan also carry the minimum marginals (TRACK), k_rw chains the group maps itself
-        if (lds_seg > set_segt[dv]) { hipFuncSetAttribute((const void *)k_seg<LC, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_seg); set_segt[dv] = lds_seg; }
-        if (lds_scan > set_scant[dv]) { hipFuncSetAttribute((const void *)k_scan<LC, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_scan); set_scant[dv] = lds_scan; }
+        lds_limit<k_seg<LC, true>>(lds_seg, dev);
+        lds_limit<k_scan<LC, true>>(lds_scan, dev);
         prof_begin(h, GH_K_SEG);
         hipLaunchKernelGGL((k_seg<LC, true>), dim3(S), dim3(SEG_THREADS), lds_seg, stream, P);
         prof_end(h, GH_K_SEG, (double)N * (double)LC * CELL * esize(h));
         hipLaunchKernelGGL((k_scan<LC, true>), dim3(G1), dim3(SEG_THREADS), lds_scan, stream, P);
         return;
     }
-    if (lds_seg > set_seg[dv]) { hipFuncSetAttribute((const void *)k_seg<LC, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_seg); set_seg[dv] = lds_seg; }
-    if (lds_scan > set_scan[dv]) { hipFuncSetAttribute((const void *)k_scan<LC, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_scan); set_scan[dv] = lds_scan; }
-    if (lds_emit > set_emit[dv]) { hipFuncSetAttribute((const void *)k_emit<LC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_emit); set_emit[dv] = lds_emit; }
+    lds_limit<k_seg<LC, false>>(lds_seg, dev);
+    lds_limit<k_scan<LC, false>>(lds_scan, dev);
+    lds_limit<k_emit<LC>>(lds_emit, dev);
     prof_begin(h, GH_K_SEG);
     hipLaunchKernelGGL((k_seg<LC, false>), dim3(S), dim3(SEG_THREADS), lds_seg, stream, P);
     // algorithmic bytes of k_seg: the conditional lookups of the extension (L history cells per step)
     prof_end(h, GH_K_SEG, (double)N * (double)LC * CELL * esize(h));
     // short memories / small windows: every segment map fits the LDS of the emitting workgroup, which composes them itself
     const size_t lds_small = max_cls(LC, [&](int R) { return emit_small_lds_bytes(N, LC, R); });
-    static const bool no_small = getenv("GH_EMIT_SMALL") && atoi(getenv("GH_EMIT_SMALL")) == 0;
+    static const bool no_small = env_off("GH_EMIT_SMALL");
     if (lds_small <= 64 * 1024 && !no_small) {
-        static std::atomic<size_t> set_small[64];
-        if (lds_small > set_small[dv]) { hipFuncSetAttribute((const void *)k_emit_small<LC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_small); set_small[dv] = lds_small; }
+        lds_limit<k_emit_small<LC>>(lds_small, dev);
         hipLaunchKernelGGL((k_emit_small<LC>), dim3(S), dim3(SEG_THREADS), lds_small, stream, P);
         return;
     }
@@ -1266,14 +1334,8 @@ static int launch_seg_walk(gh_handle *h, uint8_t *d_path, double *d_lmsel, int r
 {
     int rc = alloc_seg(h);
     if (rc) return rc;
-    seg_params P;
-    P.N = h->N; P.L = h->L; P.rearm = rearm; P.check_masks = check_masks;
-    P.G = h->lt; P.minfo = h->minfo; P.rinfo = h->rinfo; P.mt = h->cfg.marginal_term; P.nanp = h->cfg.marginal_term && h->cfg.offer_zero; P.sm = h->sm; P.st = h->dstate;
-    P.hist = h->seg_hist; P.maps = h->seg_maps; P.pmaps = h->seg_pmaps; P.gmaps = h->seg_gmaps; P.segmin = h->seg_min;
-    P.smin = h->seg_smin; P.gmin = h->seg_gmin; P.cm5snap = h->cm5snap;
-    P.rws = 0; P.W = h->W; P.esz = (int)esize(h); P.band = h->band; P.halo = h->rws ? h->seg_halo : nullptr; P.patch_off = 0;
-    P.rwflags = reinterpret_cast<int2 *>(h->seg_min + CW_MAX_SEG);
-    P.path_out = d_path; P.lmsel = d_lmsel ? d_lmsel : h->lmsel1;      // (lmsel1 exists only behind alloc_seg)
+    seg_params P = seg_make_params(h, rearm, check_masks, d_path, d_lmsel ? d_lmsel : h->lmsel1);      // (lmsel1 exists only behind alloc_seg)
+    P.halo = h->rws ? h->seg_halo : nullptr;
     if (h->L < 1 || h->L > SEG_MAX_L_NARROW) return fail(GH_ERR_STATE, "segment-parallel walk needs L <= %d", SEG_MAX_L_NARROW);
     prof_begin(h, GH_K_WALK);
     switch (h->L) {
@@ -1284,7 +1346,7 @@ static int launch_seg_walk(gh_handle *h, uint8_t *d_path, double *d_lmsel, int r
         case 5: launch_seg_lc<5>(h, P); break;
         case 6: launch_seg_lc<6>(h, P); break;      // (ranked tables only: gh_spin decides)
     }
-    prof_end(h, GH_K_WALK, (double)h->N * ((1.0 + (double)h->L) * CELL * esize(h) + 28.0));
+    prof_end(h, GH_K_WALK, walk_bytes(h->N, h->L, esize(h)));
     return post_launch(h, "k_seg/k_scan/k_emit");
 }
 
@@ -1324,26 +1386,20 @@ static void launch_rwseg_lc(gh_handle *h, seg_params P, const rws_params &Q)
     const size_t lds = off + sizeof(seg_patch);
     const size_t lds_scan = max_cls(LC, [&](int R) { return scan_lds_bytes(N, LC, R); });
     const size_t lds_emit = max_cls(LC, [&](int R) { return emit_lds_bytes(N, LC, R); });
-    static std::atomic<size_t> set_rws[64], set_scan[64], set_emit[64];
-    const int dv = h->dev & 63;
-    if (lds > set_rws[dv]) { hipFuncSetAttribute((const void *)k_rwseg<T, LC, COL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); set_rws[dv] = lds; }
-    if (lds_scan > set_scan[dv]) { hipFuncSetAttribute((const void *)k_scan<LC, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_scan); set_scan[dv] = lds_scan; }
-    if (lds_emit > set_emit[dv]) { hipFuncSetAttribute((const void *)k_emit<LC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_emit); set_emit[dv] = lds_emit; }
+    lds_limit<k_rwseg<T, LC, COL>>(lds, h->dev);
+    lds_limit<k_scan<LC, false>>(lds_scan, h->dev);
+    lds_limit<k_emit<LC>>(lds_emit, h->dev);
     P.patch_off = (int)off;
     P.rws = 1;
     prof_begin(h, GH_K_RWSEG);
     hipLaunchKernelGGL((k_rwseg<T, LC, COL>), dim3(S), dim3(SEG_THREADS), lds, h->stream, P, Q);
     // the extension's conditional lookups + what the reweight of a path reads and writes (the figure GH_K_REWEIGHT quotes)
-    const int wl = h->W < LC ? h->W : LC;
-    prof_end(h, GH_K_RWSEG, (double)N * (double)LC * CELL * esize(h) +
-             (double)(N + 1) * ((double)h->W * 2.0 * esize(h) + 1.0 + CELL * esize(h) + 2 * 64 + 88 + 8) +
-             (double)N * ((double)wl * 7 * esize(h) + (double)LC * LT_ROW * 8.0));
+    prof_end(h, GH_K_RWSEG, (double)N * (double)LC * CELL * esize(h) + reweight_bytes(N, h->W, LC, esize(h), true));
     // short memories / small windows: every segment map fits the LDS of the emitting workgroup, which composes them itself and
     // takes k_scan's look at what the reweight found as well: two launches per path
     const size_t lds_small = max_cls(LC, [&](int R) { return emit_small_lds_bytes(N, LC, R); });
-    if (lds_small <= 64 * 1024 && !(getenv("GH_EMIT_SMALL") && atoi(getenv("GH_EMIT_SMALL")) == 0)) {
-        static std::atomic<size_t> set_small[64];
-        if (lds_small > set_small[dv]) { hipFuncSetAttribute((const void *)k_emit_small<LC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_small); set_small[dv] = lds_small; }
+    if (lds_small <= 64 * 1024 && !env_off("GH_EMIT_SMALL")) {
+        lds_limit<k_emit_small<LC>>(lds_small, h->dev);
         hipLaunchKernelGGL((k_emit_small<LC>), dim3(S), dim3(SEG_THREADS), lds_small, h->stream, P);
         return;
     }
@@ -1357,14 +1413,8 @@ static int launch_rwseg(gh_handle *h, const uint8_t *d_prev, gh_path_rec *d_prev
 {
     int rc = alloc_seg(h);
     if (rc) return rc;
-    seg_params P;
-    P.N = h->N; P.L = h->L; P.rearm = 1; P.check_masks = check_masks;
-    P.G = h->lt; P.minfo = h->minfo; P.rinfo = h->rinfo; P.mt = h->cfg.marginal_term; P.nanp = h->cfg.marginal_term && h->cfg.offer_zero; P.sm = h->sm; P.st = h->dstate;
-    P.hist = h->seg_hist; P.maps = h->seg_maps; P.pmaps = h->seg_pmaps; P.gmaps = h->seg_gmaps; P.segmin = h->seg_min;
-    P.smin = h->seg_smin; P.gmin = h->seg_gmin; P.cm5snap = h->cm5snap;
-    P.rws = 1; P.W = h->W; P.esz = (int)esize(h); P.band = h->band; P.halo = h->seg_halo; P.patch_off = 0;
-    P.rwflags = reinterpret_cast<int2 *>(h->seg_min + CW_MAX_SEG);
-    P.path_out = d_path; P.lmsel = d_lmsel;
+    seg_params P = seg_make_params(h, 1, check_masks, d_path, d_lmsel);
+    P.rws = 1; P.halo = h->seg_halo;
     rws_params Q;
     Q.band = h->band; Q.cnt = h->cnt; Q.marg = h->marg; Q.minfo = h->minfo; Q.rinfo = h->need_rinfo ? h->rinfo : nullptr; Q.G = h->lt;
     Q.nvalid = h->nvalid; Q.cmask = h->cmask; Q.path = d_prev; Q.min_remove = min_remove;
@@ -1372,16 +1422,16 @@ static int launch_rwseg(gh_handle *h, const uint8_t *d_prev, gh_path_rec *d_prev
     Q.rec = d_prev_rec; Q.cond_mode = h->cfg.cond_mode; Q.offer_zero = h->cfg.offer_zero;
     if (h->L < 1 || h->L > SEG_MAX_L_NARROW) return fail(GH_ERR_STATE, "k_rwseg needs L <= %d", SEG_MAX_L_NARROW);   // before the bracket opens
     prof_begin(h, GH_K_WALK);
-    const bool f64 = h->cfg.storage == GH_STORAGE_F64;
     const bool col = h->cfg.cond_mode == GH_COND_C || h->cfg.cond_mode == GH_COND_E;
-    switch (h->L) {
-#define RWS_CASE(n) case n: if (f64) { if (col) launch_rwseg_lc<double, n, true>(h, P, Q); else launch_rwseg_lc<double, n, false>(h, P, Q); } \
-                            else { if (col) launch_rwseg_lc<float, n, true>(h, P, Q); else launch_rwseg_lc<float, n, false>(h, P, Q); } break;
-        RWS_CASE(1) RWS_CASE(2) RWS_CASE(3) RWS_CASE(4) RWS_CASE(5) RWS_CASE(6)
+    with_storage(h, [&](auto z) {
+        using T = decltype(z);
+        switch (h->L) {
+#define RWS_CASE(n) case n: if (col) launch_rwseg_lc<T, n, true>(h, P, Q); else launch_rwseg_lc<T, n, false>(h, P, Q); break;
+            RWS_CASE(1) RWS_CASE(2) RWS_CASE(3) RWS_CASE(4) RWS_CASE(5) RWS_CASE(6)
 #undef RWS_CASE
-        default: return fail(GH_ERR_STATE, "k_rwseg needs L <= %d", SEG_MAX_L_NARROW);
-    }
-    prof_end(h, GH_K_WALK, (double)h->N * ((1.0 + (double)h->L) * CELL * esize(h) + 28.0));
+        }
+    });
+    prof_end(h, GH_K_WALK, walk_bytes(h->N, h->L, esize(h)));
     // (what launch_reweight_marg notes behind a fused reweight: the table is current up to the rows this path's reweight wrote)
     h->lt_inc_path = d_prev;
     h->lt_inc_seg = true;
@@ -1403,9 +1453,7 @@ static int launch_walk(gh_handle *h, uint8_t *d_path, gh_path_rec *d_rec, double
     P.path_out = d_path; P.rec = d_rec; P.st = h->dstate; P.min_remove = min_remove; P.sm = h->sm;
     prof_begin(h, GH_K_WALK);
     launch_walk_any(h->wmode, h->N, h->L, P, h->stream, 1, nullptr, 0);
-    // algorithmic bytes, SURVEY 8(d): per step the marginal cell + L history cells (49 elements each) + the original
-    // marginals (7 x 4 B).  What this build's layout needs per step is one table row: N * (L * 40 + 25) bytes.
-    prof_end(h, GH_K_WALK, (double)h->N * ((1.0 + (double)h->L) * CELL * esize(h) + 28.0));
+    prof_end(h, GH_K_WALK, walk_bytes(h->N, h->L, esize(h)));
     { int rc_ = post_launch(h, "k_walk"); if (rc_) return rc_; }
     return GH_OK;
 }
@@ -1431,17 +1479,31 @@ static int ensure_partial(gh_handle *h, int nb, int slots)
 // round), else 8; blocks per path accordingly (also the stride of the per-path partial sums of the removed mass)
 // (16: row conditionals with bands up to 32 and at most 16 lags -- the distances beyond 16 take a second round, the table
 // entries are dealt out over the group anyway, and the marginals, 7 lanes of every group, cost a wavefront half as much)
+// the to-major copy of the band (column conditionals): allocated on first use and converted on `st` when something else wrote the
+// band since; the caller marks it in step (tband_epoch) -- at once, or behind the kernel that keeps both
+static int ensure_tband(gh_handle *h, hipStream_t st)
+{
+    const size_t nel = h->n_cells * CELL;
+    if (!h->tband && hipMalloc(&h->tband, nel * esize(h)) != hipSuccess) { h->tband = nullptr; return fail(GH_ERR_NOMEM, "hipMalloc for the to-major band failed"); }
+    if (h->tband_epoch != h->band_epoch)
+        with_storage(h, [&](auto z) {
+            using T = decltype(z);
+            hipLaunchKernelGGL(k_band_to_major<T>, dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, st, (const T *)h->band, (T *)h->tband, nel, h->W);
+        });
+    return GH_OK;
+}
+
 static bool rw_col(const gh_handle *h) { return h->cfg.cond_mode == GH_COND_C || h->cfg.cond_mode == GH_COND_E; }
 // column conditionals beyond the 8-lane groups: k_rw reads its columns from a to-major copy of the band (GH_RW_TBAND=0: from the staged block)
 static bool rw_tband(const gh_handle *h)
 {
-    static const bool off = getenv("GH_RW_TBAND") && atoi(getenv("GH_RW_TBAND")) == 0;
+    static const bool off = env_off("GH_RW_TBAND");
     return rw_col(h) && (h->W > 8 || h->L > 8) && !off;
 }
 static int rw_lanes(const gh_handle *h)
 {
     if (!(h->W > 8 || h->L > 8)) return 8;
-    static const bool no16 = getenv("GH_RW_LP16") && atoi(getenv("GH_RW_LP16")) == 0;
+    static const bool no16 = env_off("GH_RW_LP16");
     return (h->W <= 32 && h->L <= 16 && !no16 && (!rw_col(h) || rw_tband(h))) ? 16 : 32;
 }
 static int rw_blocks(const gh_handle *h, bool seg) { return (int)(((size_t)(h->N + 1) * (seg ? rw_lanes(h) : 8) + 255) / 256); }
@@ -1469,39 +1531,11 @@ static int launch_reweight_marg(gh_handle *h, const uint8_t *d_path, double rati
     prof_begin(h, GH_K_REWEIGHT);
     if (seg) {
         // behind a segment-parallel walk (L <= SEG_MAX_L <= 8: one table row per lane): segwalk.hpp's k_rw
-#define GH_RW_LAUNCH(T, LP, COL, FZ)                                                                                              \
-    do {                                                                                                                          \
-        /* COL: the band block of the workgroup's positions staged in LDS when it fits (k_rw) */                                   \
-        const size_t blk_b = (size_t)(256 / LP) * NSYM * h->W * NSYM * sizeof(T);                                                 \
-        /* | 2: `cnt` holds the row sums of the band as it stands (k_rw takes the rows a reweight does not touch from there) */     \
-        const int stage = ((COL && !use_tb && blk_b <= 64 * 1024 && !(getenv("GH_RW_STAGE") && atoi(getenv("GH_RW_STAGE")) == 0)) ? 1 : 0) |  \
-                          ((!h->dirty_marg && !(getenv("GH_RW_CNT") && atoi(getenv("GH_RW_CNT")) == 0)) ? 2 : 0) | ((COL && use_tb) ? 4 : 0); \
-        const size_t lds_b = fuse_lds + ((stage & 1) ? blk_b : 0);                                                                \
-        static std::atomic<size_t> set_lds[64];                                                                                   \
-        if (lds_b > set_lds[h->dev & 63]) {                                                                                       \
-            hipFuncSetAttribute((const void *)k_rw<T, LP, COL, FZ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);      \
-            set_lds[h->dev & 63] = lds_b;                                                                                         \
-        }                                                                                                                         \
-        hipLaunchKernelGGL((k_rw<T, LP, COL, FZ>), dim3(nb), dim3(block), lds_b, h->stream, (T *)h->band, h->N, h->W, h->cnt, h->marg, h->nvalid, \
-                           h->cmask, h->minfo, h->dstate, d_path, ratio, partial, lt_rows, h->L, h->cfg.cond_mode,                \
-                           (const double *)h->seg_min, d_rec, nseg_arg, h->sm, h->cfg.offer_zero, h->need_rinfo ? h->rinfo : (double *)nullptr, stage, fz, (int)fuse_lds, \
-                           (T *)(use_tb ? h->tband : nullptr));                                                                   \
-    } while (0)
-#define GH_RW_LAUNCH2(T, LP) do { if (col) GH_RW_LAUNCH(T, LP, true, false); else GH_RW_LAUNCH(T, LP, false, false); } while (0)
-#define GH_RW_LAUNCHF(T) do { if (col) GH_RW_LAUNCH(T, 8, true, true); else GH_RW_LAUNCH(T, 8, false, true); } while (0)
         const bool wide = rw_lanes(h) == 32, mid = rw_lanes(h) == 16;
         const bool col = rw_col(h);                         // the table entries a reweighted cell feeds: a column
         // the to-major copy: made (or made again, when something else wrote the band since) right here, kept by the kernel
         const bool use_tb = rw_tband(h) && !(h->fuse && nseg_arg == 0);
-        if (use_tb) {
-            const size_t nel = h->n_cells * CELL;
-            if (!h->tband && hipMalloc(&h->tband, nel * esize(h)) != hipSuccess) { h->tband = nullptr; return fail(GH_ERR_NOMEM, "hipMalloc for the to-major band failed"); }
-            if (h->tband_epoch != h->band_epoch) {
-                const unsigned nbt = (unsigned)((nel + 255) / 256);
-                if (h->cfg.storage == GH_STORAGE_F64) hipLaunchKernelGGL(k_band_to_major<double>, dim3(nbt), dim3(256), 0, h->stream, (const double *)h->band, (double *)h->tband, nel, h->W);
-                else hipLaunchKernelGGL(k_band_to_major<float>, dim3(nbt), dim3(256), 0, h->stream, (const float *)h->band, (float *)h->tband, nel, h->W);
-            }
-        }
+        if (use_tb) { int rc_ = ensure_tband(h, h->stream); if (rc_) return rc_; }
         // behind k_seg + k_scan without a k_emit (h->fuse): the kernel finds its picks itself and writes the path to d_path / d_lmsel
         fuse_params fz;
         memset(&fz, 0, sizeof fz);
@@ -1511,32 +1545,41 @@ static int launch_reweight_marg(gh_handle *h, const uint8_t *d_path, double rati
             fz.path_out = const_cast<uint8_t *>(d_path); fz.lmsel = d_lmsel;
             fuse_lds = h->fuse_lds;
         }
-        if (fz.hist) {                                      // (three-launch spins: lane groups of 8 only, gh_spin decides)
-            if (h->cfg.storage == GH_STORAGE_F64) GH_RW_LAUNCHF(double); else GH_RW_LAUNCHF(float);
-        } else if (mid) { if (h->cfg.storage == GH_STORAGE_F64) GH_RW_LAUNCH2(double, 16); else GH_RW_LAUNCH2(float, 16); }
-        else if (h->cfg.storage == GH_STORAGE_F64) { if (wide) GH_RW_LAUNCH2(double, 32); else GH_RW_LAUNCH2(double, 8); }
-        else { if (wide) GH_RW_LAUNCH2(float, 32); else GH_RW_LAUNCH2(float, 8); }
-#undef GH_RW_LAUNCHF
+        with_storage(h, [&](auto z) {
+            using T = decltype(z);
+#define GH_RW_LAUNCH(LP, COL, FZ)                                                                                                 \
+    do {                                                                                                                          \
+        /* COL: the band block of the workgroup's positions staged in LDS when it fits (k_rw) */                                   \
+        const size_t blk_b = (size_t)(256 / LP) * NSYM * h->W * NSYM * sizeof(T);                                                 \
+        /* | 2: `cnt` holds the row sums of the band as it stands (k_rw takes the rows a reweight does not touch from there) */     \
+        const int stage = ((COL && !use_tb && blk_b <= 64 * 1024 && !env_off("GH_RW_STAGE")) ? 1 : 0) |                           \
+                          ((!h->dirty_marg && !env_off("GH_RW_CNT")) ? 2 : 0) | ((COL && use_tb) ? 4 : 0);                        \
+        const size_t lds_b = fuse_lds + ((stage & 1) ? blk_b : 0);                                                                \
+        lds_limit<k_rw<T, LP, COL, FZ>>(lds_b, h->dev);                                                                           \
+        hipLaunchKernelGGL((k_rw<T, LP, COL, FZ>), dim3(nb), dim3(block), lds_b, h->stream, (T *)h->band, h->N, h->W, h->cnt, h->marg, h->nvalid, \
+                           h->cmask, h->minfo, h->dstate, d_path, ratio, partial, lt_rows, h->L, h->cfg.cond_mode,                \
+                           (const double *)h->seg_min, d_rec, nseg_arg, h->sm, h->cfg.offer_zero, h->need_rinfo ? h->rinfo : nullptr, stage, fz, (int)fuse_lds, \
+                           (T *)(use_tb ? h->tband : nullptr));                                                                   \
+    } while (0)
+#define GH_RW_LAUNCH2(LP) do { if (col) GH_RW_LAUNCH(LP, true, false); else GH_RW_LAUNCH(LP, false, false); } while (0)
+            if (fz.hist) {                                  // (three-launch spins: lane groups of 8 only, gh_spin decides)
+                if (col) GH_RW_LAUNCH(8, true, true); else GH_RW_LAUNCH(8, false, true);
+            } else if (mid) GH_RW_LAUNCH2(16);
+            else if (wide) GH_RW_LAUNCH2(32);
+            else GH_RW_LAUNCH2(8);
 #undef GH_RW_LAUNCH2
 #undef GH_RW_LAUNCH
-    } else if (h->cfg.storage == GH_STORAGE_F64)
-        hipLaunchKernelGGL((k_marg<double, true>), dim3(nb), dim3(block), 0, h->stream, (double *)h->band, h->N, h->W,
-                           h->cnt, h->marg, h->nvalid, h->cmask, h->minfo, h->dstate, (const win_desc *)nullptr,
-                           d_path, ratio, use_state, partial, 0, lt_rows, h->L, h->cfg.cond_mode,
-                           (const double *)nullptr, (gh_path_rec *)nullptr, h->sm, h->cfg.offer_zero, h->need_rinfo ? h->rinfo : (double *)nullptr);
-    else
-        hipLaunchKernelGGL((k_marg<float, true>), dim3(nb), dim3(block), 0, h->stream, (float *)h->band, h->N, h->W,
-                           h->cnt, h->marg, h->nvalid, h->cmask, h->minfo, h->dstate, (const win_desc *)nullptr,
-                           d_path, ratio, use_state, partial, 0, lt_rows, h->L, h->cfg.cond_mode,
-                           (const double *)nullptr, (gh_path_rec *)nullptr, h->sm, h->cfg.offer_zero, h->need_rinfo ? h->rinfo : (double *)nullptr);
+        });
+    } else {
+        marg_args a = marg_of(h);
+        a.rw_path = d_path; a.ratio = ratio; a.use_state_ratio = use_state; a.partial = partial; a.G = lt_rows; a.L = h->L;
+        a.cond_mode = h->cfg.cond_mode;
+        launch_marg<true>(h, dim3(nb), h->stream, a);
+    }
     if (slot < 0)
         hipLaunchKernelGGL(k_reweight_finish, dim3(1), dim3(256), 0, h->stream, partial, nb, h->dstate, use_state, d_rec,
                            (const win_desc *)nullptr, 0);
-    // algorithmic bytes: the reweighted elements (read+write) + the marginal pass (read cell (p,p+1), write the tables)
-    // (+ one band row read and L x 5 table entries written per (source, lag) when the table rows are rewritten too)
-    const int wl = h->W < h->L ? h->W : h->L;
-    prof_end(h, GH_K_REWEIGHT, (double)(h->N + 1) * ((double)h->W * 2.0 * esize(h) + 1.0 + CELL * esize(h) + 2 * 64 + 88 + 8) +
-                               (lt_ok ? (double)h->N * ((double)wl * 7 * esize(h) + (double)h->L * LT_ROW * 8.0) : 0.0));
+    prof_end(h, GH_K_REWEIGHT, reweight_bytes(h->N, h->W, h->L, esize(h), lt_ok));
     { int rc_ = post_launch(h, "k_marg<reweight>"); if (rc_) return rc_; }
     h->lt_inc_path = lt_ok ? d_path : nullptr;
     h->lt_inc_seg = seg;
@@ -1626,7 +1669,7 @@ static cw_params cw_make_params(gh_handle *h, uint8_t *d_path, double *d_lmsel)
     // walker -- 736 us per path without run-on at L = 33, 855..897 with one to three segments of it)
     // (33..64 lags over ranks and 22..40 over the symbols go through k_cwalk2 since round 6: k_cwalk's step, and its run-on)
     if (cw_digit_mode(h) && !cw2_ok(h)) runon = 0;
-    if (getenv("GH_CW_RUNON")) runon = atoi(getenv("GH_CW_RUNON"));
+    runon = env_int("GH_CW_RUNON", runon);
     if (runon > CW_RUNON) runon = CW_RUNON;
     const bool no_runon = runon <= 0;
     P.runon = runon;
@@ -1662,22 +1705,14 @@ static cw_params cw_make_params(gh_handle *h, uint8_t *d_path, double *d_lmsel)
 template <int LC, int R>
 static void launch_cwalk_lc(const cw_params &P, hipStream_t stream, int S, int dev)
 {
-    static std::atomic<bool> set[64];
-    if (!set[dev & 63]) {
-        hipFuncSetAttribute((const void *)k_cwalk<LC, R>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cw_lds_bytes(LC, R));
-        set[dev & 63] = true;
-    }
+    lds_limit<k_cwalk<LC, R>>(cw_lds_bytes(LC, R), dev);
     hipLaunchKernelGGL((k_cwalk<LC, R>), dim3(S), dim3(CW_K * cw_lanes(R)), cw_lds_bytes(LC, R), stream, P);
 }
 
 template <int LC, int R = 4>
 static void launch_cwalk2_lc(const cw_params &P, hipStream_t stream, int S, int dev)
 {
-    static std::atomic<bool> set[64];
-    if (!set[dev & 63]) {
-        hipFuncSetAttribute((const void *)k_cwalk2<LC, R>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cw2_lds_bytes(LC, R));
-        set[dev & 63] = true;
-    }
+    lds_limit<k_cwalk2<LC, R>>(cw2_lds_bytes(LC, R), dev);
     hipLaunchKernelGGL((k_cwalk2<LC, R>), dim3(S), dim3(CW_K * cw_lanes(R)), cw2_lds_bytes(LC, R), stream, P);
 }
 
@@ -1687,7 +1722,7 @@ static int launch_cw_path(gh_handle *h, uint8_t *d_path, double *d_lmsel, int ro
     const cw_geom g = cw_geometry(h->N, h->L);
     cw_params P = cw_make_params(h, d_path, d_lmsel);
     if (h->cw_round_cap > 0 && rounds > h->cw_round_cap) rounds = h->cw_round_cap;
-    const bool skip0 = !resume && !(getenv("GH_CW_SKIP0") && atoi(getenv("GH_CW_SKIP0")) == 0);      // (GH_CW_SKIP0=0: A/B, tests)
+    const bool skip0 = !resume && !env_off("GH_CW_SKIP0");      // (GH_CW_SKIP0=0: A/B, tests)
     if (!cw_digit_mode(h) && (h->L < CW_MIN_L || h->L > CW_MAX_L)) return fail(GH_ERR_STATE, "candidate-pool walk needs %d <= L <= %d", CW_MIN_L, CW_MAX_LG);
     prof_begin(h, GH_K_WALK);
     for (int r = 0; r < rounds; r++) {
@@ -1723,15 +1758,9 @@ static int launch_cw_path(gh_handle *h, uint8_t *d_path, double *d_lmsel, int ro
                 default: launch_cwalk2_lc<64>(P, h->stream, g.S, h->dev); break;
             }
         } else if (cw_digit_mode(h)) {
-            static std::atomic<size_t> set_g[2][64];
-            const int R = h->cw_wide ? 5 : 4;
-            const size_t lds_g = cwg_lds_bytes(h->L, R);
-            if (lds_g > set_g[R - 4][h->dev & 63]) {
-                hipFuncSetAttribute(R == 4 ? (const void *)k_cwalkg<4> : (const void *)k_cwalkg<5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_g);
-                set_g[R - 4][h->dev & 63] = lds_g;
-            }
-            if (!h->cw_wide) hipLaunchKernelGGL((k_cwalkg<4>), dim3(g.S), dim3(CW_K * cw_lanes(4)), lds_g, h->stream, P);
-            else hipLaunchKernelGGL((k_cwalkg<5>), dim3(g.S), dim3(CW_K * cw_lanes(5)), lds_g, h->stream, P);
+            const size_t lds_g = cwg_lds_bytes(h->L, h->cw_wide ? 5 : 4);
+            if (!h->cw_wide) { lds_limit<k_cwalkg<4>>(lds_g, h->dev); hipLaunchKernelGGL((k_cwalkg<4>), dim3(g.S), dim3(CW_K * cw_lanes(4)), lds_g, h->stream, P); }
+            else { lds_limit<k_cwalkg<5>>(lds_g, h->dev); hipLaunchKernelGGL((k_cwalkg<5>), dim3(g.S), dim3(CW_K * cw_lanes(5)), lds_g, h->stream, P); }
         } else
         switch (h->L) {
             // (the table over the symbols: 3 bits per pick, CW_MAX_L5 lags in a state)
@@ -1751,7 +1780,7 @@ static int launch_cw_path(gh_handle *h, uint8_t *d_path, double *d_lmsel, int ro
         hipLaunchKernelGGL(k_cscan, dim3(1), dim3(1024), 0, h->stream, P);
     }
     hipLaunchKernelGGL(k_cemit, dim3(g.S), dim3(256), 0, h->stream, P);
-    prof_end(h, GH_K_WALK, (double)h->N * ((1.0 + (double)h->L) * CELL * esize(h) + 28.0));
+    prof_end(h, GH_K_WALK, walk_bytes(h->N, h->L, esize(h)));
     return post_launch(h, "k_cwalk/k_cscan/k_cemit");
 }
 
@@ -1870,20 +1899,16 @@ extern "C" int gh_generate_path(gh_t *h, const gh_t *original, uint8_t *path_out
     if ((rc = launch_walk(h, h->d_path, h->d_rec, 0.0, 0))) return rc;
     if (seg_ok(h->wmode, h->L)) {
         // close the record (hole / minimum marginal), then the two likelihood sums
-        seg_params P;
-        memset(&P, 0, sizeof P);
-        P.N = h->N; P.L = h->L; P.st = h->dstate; P.segmin = h->seg_min;
-        hipLaunchKernelGGL(k_seg_fin, dim3(1), dim3(256), 0, h->stream, P, h->d_rec, 0.0, 0);
+        hipLaunchKernelGGL(k_seg_fin, dim3(1), dim3(256), 0, h->stream, seg_make_params(h, 0, 0, nullptr, nullptr), h->d_rec, 0.0, 0);
         hipLaunchKernelGGL(k_hp, dim3(1, 2), dim3(64), 0, h->stream, (const double *)h->lmsel1, (size_t)0, (const uint8_t *)h->d_path,
                            (size_t)0, (const double *)h->minfo, h->N, (const dev_state *)h->dstate, h->d_rec, h->sm);
         if ((rc = post_launch(h, "k_seg_fin/k_hp"))) return rc;
     }
     dev_state hs;
     gh_path_rec rec;
-    HIPCHK(hipMemcpyAsync(&hs, h->dstate, sizeof hs, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(&rec, h->d_rec, sizeof rec, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(path_out, h->d_path, (size_t)h->N + 1, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    if ((rc = read_state(h, &hs))) return rc;
     *hole_at = hs.stop ? hs.hole_at : 0;
     if (!hs.stop) {
         if (hp_current) *hp_current = rec.hp_current;
@@ -1990,10 +2015,7 @@ static int spin_candidate_pools(gh_handle *h, const spin_io &io, dev_state &hs, 
     // what follows the kernels of a path: the fused reweight (which also closes the path's record), or only the closing
     auto finish_path = [&](uint8_t *pth, gh_path_rec *rec, int slot, bool chained) -> int {
         if (!io.no_reweight) return launch_reweight_marg(h, pth, min_remove, 1, rec, slot, true, chained, cg.S);
-        seg_params SP;
-        memset(&SP, 0, sizeof SP);
-        SP.N = h->N; SP.L = h->L; SP.st = h->dstate; SP.segmin = h->seg_min;
-        hipLaunchKernelGGL(k_seg_fin, dim3(1), dim3(256), 0, h->stream, SP, rec, min_remove, cg.S);
+        hipLaunchKernelGGL(k_seg_fin, dim3(1), dim3(256), 0, h->stream, seg_make_params(h, 0, 0, nullptr, nullptr), rec, min_remove, cg.S);
         return post_launch(h, "k_seg_fin");
     };
     const int zero2[2] = {0, 0};
@@ -2030,10 +2052,7 @@ static int spin_candidate_pools(gh_handle *h, const spin_io &io, dev_state &hs, 
     if (rc == GH_OK) rc = ensure_lt(h);
     if (rc == GH_OK) {
         dev_state look;
-        e = hipMemcpyAsync(&look, h->dstate, sizeof look, hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = fail(GH_ERR_HIP, "gh_spin failed: %s", hipGetErrorString(e));
-        else look_at_layout(look.ranked);
+        if ((rc = read_state(h, &look)) == GH_OK) look_at_layout(look.ranked);
     }
     int done = 0;
     int CHUNK = 8, clean = 0;        // paths queued between two looks at the device state: grows while every chain closes
@@ -2078,9 +2097,7 @@ static int spin_candidate_pools(gh_handle *h, const spin_io &io, dev_state &hs, 
             }
             if (rc) break;
         }
-        e = hipMemcpyAsync(&hs, h->dstate, sizeof hs, hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) { rc = fail(GH_ERR_HIP, "gh_spin failed: %s", hipGetErrorString(e)); break; }
+        if ((rc = read_state(h, &hs))) break;
         if (getenv("GH_PRINT_STATE"))
             fprintf(stderr, "gh_spin(cw): n_done %d stop %d lt_stale %d cw_unres %d open_at %d rounds %d  closed in round 0/1/2/3/4+: %llu %llu %llu %llu %llu\n", hs.n_done, hs.stop, hs.lt_stale,
                     hs.cw_unres, hs.cw_open_at, h->cw_rounds, hs.dbg8[0], hs.dbg8[1], hs.dbg8[2], hs.dbg8[3], hs.dbg8[4]);
@@ -2131,9 +2148,7 @@ static int spin_candidate_pools(gh_handle *h, const spin_io &io, dev_state &hs, 
                         if ((rc = launch_cw_path(h, d_paths + n1 * done, h->spin_lmsel + n1 * done, more, 0, true))) break;
                         if ((rc = finish_path(d_paths + n1 * done, d_recs + done, done, false))) break;
                         h->cw_stat[2] += more;
-                        e = hipMemcpyAsync(&hs, h->dstate, sizeof hs, hipMemcpyDeviceToHost, h->stream);
-                        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-                        if (e != hipSuccess) { rc = fail(GH_ERR_HIP, "gh_spin failed: %s", hipGetErrorString(e)); break; }
+                        if ((rc = read_state(h, &hs))) break;
                         closed = !hs.cw_unres && hs.n_done > done;
                         if (hs.cw_unres) {
                             e = hipMemcpyAsync(&h->dstate->lt_stale, zero2, sizeof zero2, hipMemcpyHostToDevice, h->stream);
@@ -2146,9 +2161,7 @@ static int spin_candidate_pools(gh_handle *h, const spin_io &io, dev_state &hs, 
                 if (!closed) {
                     h->cw_stamp++;
                     if ((rc = cw_serial_path(h, d_paths + n1 * done, d_recs + done, h->spin_lmsel + n1 * done, min_remove, done, 1, !io.no_reweight))) break;
-                    e = hipMemcpyAsync(&hs, h->dstate, sizeof hs, hipMemcpyDeviceToHost, h->stream);
-                    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-                    if (e != hipSuccess) { rc = fail(GH_ERR_HIP, "gh_spin failed: %s", hipGetErrorString(e)); break; }
+                    if ((rc = read_state(h, &hs))) break;
                 }
                 done = hs.n_done;
                 if (hs.stop) break;
@@ -2166,12 +2179,8 @@ static int spin_candidate_pools(gh_handle *h, const spin_io &io, dev_state &hs, 
                            (const double *)h->minfo, h->N, (const dev_state *)h->dstate, d_recs, h->sm);
         if (!io.no_reweight) hipLaunchKernelGGL(k_reweight_finish_all, dim3(done), dim3(256), 0, h->stream, h->partial, nb, h->dstate, d_recs);
         rc = post_launch(h, "k_hp/k_reweight_finish_all");
-        if (rc == GH_OK) {
-            e = hipMemcpyAsync(&hs, h->dstate, sizeof hs, hipMemcpyDeviceToHost, h->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-            if (e != hipSuccess) rc = fail(GH_ERR_HIP, "gh_spin failed: %s", hipGetErrorString(e));
-            else if (hs.n_done > 0) rc = results_to_host(h, paths_out, d_paths, n1 * hs.n_done, recs, d_recs, sizeof(gh_path_rec) * hs.n_done);
-        }
+        if (rc == GH_OK && (rc = read_state(h, &hs)) == GH_OK && hs.n_done > 0)
+            rc = results_to_host(h, paths_out, d_paths, n1 * hs.n_done, recs, d_recs, sizeof(gh_path_rec) * hs.n_done);
     }
     *first_out = first;
     *gave_up = cw_gave_up;
@@ -2196,17 +2205,11 @@ extern "C" int gh_spin(gh_t *h, int max_paths, double min_remove, uint8_t *paths
     rc = GH_OK;
     bool seg = seg_ok(h->wmode, h->L);
     h->seg6 = false;
-    if (rc == GH_OK && !seg && h->wmode == WM_SEG && h->L == SEG_MAX_L_NARROW && !(getenv("GH_SEG6") && atoi(getenv("GH_SEG6")) == 0)) {
+    if (rc == GH_OK && !seg && h->wmode == WM_SEG && h->L == SEG_MAX_L_NARROW && !env_off("GH_SEG6")) {
         // 4^6 states can still be enumerated -- 5^6 cannot: look at the layout k_lt chose for this tensor (a window that is
         // narrow stays narrow: candidates only ever disappear)
-        rc = ensure_lt(h);
         dev_state look;
-        if (rc == GH_OK) {
-            e = hipMemcpyAsync(&look, h->dstate, sizeof look, hipMemcpyDeviceToHost, h->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-            if (e != hipSuccess) rc = fail(GH_ERR_HIP, "gh_spin failed: %s", hipGetErrorString(e));
-            else if (look.ranked) { seg = true; h->seg6 = true; }
-        }
+        if ((rc = ensure_lt(h)) == GH_OK && (rc = read_state(h, &look)) == GH_OK && look.ranked) { seg = true; h->seg6 = true; }
     }
     // Spins over the enumerated states run without k_emit where the group maps fit k_rw's LDS beside everything else
     // (1024 states: 32 KB; the five-symbol radix from 5^5 states on, and 4^6, keep k_emit) and the band is not wider than
@@ -2216,25 +2219,19 @@ extern "C" int gh_spin(gh_t *h, int max_paths, double min_remove, uint8_t *paths
     // boundary (6.8 us) go, the prologue k_rw needs instead (group maps to LDS, the chain, one more round trip) costs 6.5 us,
     // and carrying the minima through k_seg / k_scan another 2.9 us: 40.8 against 38.7 us per path.  So it is opt-in:
     // GH_FUSE=1 (large windows) or 2 (every window the maps fit; the tests).
-    if (rc == GH_OK && seg && h->need_rinfo && h->W <= RW_FUSE_HALO && rw_lanes(h) == 8 && getenv("GH_FUSE") && atoi(getenv("GH_FUSE")) >= 1) {
-        rc = ensure_lt(h);
+    if (rc == GH_OK && seg && h->need_rinfo && h->W <= RW_FUSE_HALO && rw_lanes(h) == 8 && env_int("GH_FUSE", 0) >= 1) {
         dev_state look;
-        if (rc == GH_OK) {
-            e = hipMemcpyAsync(&look, h->dstate, sizeof look, hipMemcpyDeviceToHost, h->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-            if (e != hipSuccess) rc = fail(GH_ERR_HIP, "gh_spin failed: %s", hipGetErrorString(e));
-            else {
-                const int R = look.ranked ? 4 : 5;
-                const int ppb = 256 / rw_lanes(h);
-                // (windows whose segment maps all fit one workgroup's LDS keep k_emit_small: three launches as well, and a lighter k_rw)
-                const bool small = emit_small_lds_bytes(h->N, h->L, R) <= 64 * 1024 && !(getenv("GH_EMIT_SMALL") && atoi(getenv("GH_EMIT_SMALL")) == 0);
-                const bool force = getenv("GH_FUSE") && atoi(getenv("GH_FUSE")) == 2;      // (tests: fused whatever the size)
-                if ((!small || force) && seg_radix_ok(R, h->L) && rw_fuse_lds_bytes(h->N, h->L, R, ppb, h->W) <= 64 * 1024 && (rc = alloc_seg(h)) == GH_OK) {
-                    h->fuse = true;
-                    h->fuse_lds = rw_fuse_lds_bytes(h->N, h->L, R, ppb, h->W);
-                    // (this spin walks the enumerated states: whatever k_classify found before the flow was chosen does not apply)
-                    if (hipMemsetAsync(&h->dstate->maxstates, 0, sizeof(int), h->stream) != hipSuccess) rc = fail(GH_ERR_HIP, "gh_spin failed: hipMemsetAsync");
-                }
+        if ((rc = ensure_lt(h)) == GH_OK && (rc = read_state(h, &look)) == GH_OK) {
+            const int R = look.ranked ? 4 : 5;
+            const int ppb = 256 / rw_lanes(h);
+            // (windows whose segment maps all fit one workgroup's LDS keep k_emit_small: three launches as well, and a lighter k_rw)
+            const bool small = emit_small_lds_bytes(h->N, h->L, R) <= 64 * 1024 && !env_off("GH_EMIT_SMALL");
+            const bool force = env_int("GH_FUSE", 0) == 2;      // (tests: fused whatever the size)
+            if ((!small || force) && seg_radix_ok(R, h->L) && rw_fuse_lds_bytes(h->N, h->L, R, ppb, h->W) <= 64 * 1024 && (rc = alloc_seg(h)) == GH_OK) {
+                h->fuse = true;
+                h->fuse_lds = rw_fuse_lds_bytes(h->N, h->L, R, ppb, h->W);
+                // (this spin walks the enumerated states: whatever k_classify found before the flow was chosen does not apply)
+                if (hipMemsetAsync(&h->dstate->maxstates, 0, sizeof(int), h->stream) != hipSuccess) rc = fail(GH_ERR_HIP, "gh_spin failed: hipMemsetAsync");
             }
         }
     }
@@ -2242,17 +2239,16 @@ extern "C" int gh_spin(gh_t *h, int max_paths, double min_remove, uint8_t *paths
     // at most 128 positions per workgroup with the halo; behind it k_scan + k_emit, or k_emit_small alone in small windows.
     h->rws = false;
     int rws_S = 0;
-    if (rc == GH_OK && seg && !h->fuse && !h->lt_full && rw_lanes(h) == 8 &&
-        !(getenv("GH_RWSEG") && atoi(getenv("GH_RWSEG")) == 0)) {
+    if (rc == GH_OK && seg && !h->fuse && !h->lt_full && rw_lanes(h) == 8 && !env_off("GH_RWSEG")) {
         const bool five = seg_radix_ok(5, h->L);
         const seg_geom g4 = seg_geometry(h->N, h->L, 4), g5 = five ? seg_geometry(h->N, h->L, 5) : g4;
         const bool small = (five ? max2(emit_small_lds_bytes(h->N, h->L, 4), emit_small_lds_bytes(h->N, h->L, 5)) : emit_small_lds_bytes(h->N, h->L, 4)) <= 64 * 1024 &&
-                           !(getenv("GH_EMIT_SMALL") && atoi(getenv("GH_EMIT_SMALL")) == 0);
+                           !env_off("GH_EMIT_SMALL");
         const int longest = g4.seglen > g5.seglen ? g4.seglen : g5.seglen;
         // (... and the kernel's LDS must fit: the column conditionals stage the band blocks of all those positions -- long
         // segments of a wide band in binary64 do not)
         // (small windows -- k_emit_small behind k_rwseg, two launches per path -- unless GH_RWSEG_SMALL=0)
-        const bool small_ok = !(getenv("GH_RWSEG_SMALL") && atoi(getenv("GH_RWSEG_SMALL")) == 0);
+        const bool small_ok = !env_off("GH_RWSEG_SMALL");
         if ((!small || small_ok) && longest + h->L + 1 <= SEG_THREADS / 8 && rws_patch_off(h, h->L) + sizeof(seg_patch) <= RWS_LDS_MAX &&
             (rc = alloc_seg(h)) == GH_OK) {
             rws_S = g4.S > g5.S ? g4.S : g5.S;
@@ -2335,10 +2331,7 @@ extern "C" int gh_spin(gh_t *h, int max_paths, double min_remove, uint8_t *paths
             if (sr < 0) { rc = sr; break; }
             staged = sr == GH_OK;
         }
-        if (!staged) {
-            e = hipMemcpyAsync(&hs, h->dstate, sizeof hs, hipMemcpyDeviceToHost, h->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        }
+        if (!staged && (rc = read_state(h, &hs))) break;
         if (getenv("GH_PRINT_STATE"))
             fprintf(stderr, "gh_spin: stop %d hole_at %d n_done %d first_hole %d cur_hole %d lt_stale %d cm_same %d narrow %d ranked %d\n", hs.stop, hs.hole_at,
                     hs.n_done, hs.first_hole, hs.cur_hole, hs.lt_stale, hs.cm_same, hs.narrow, hs.ranked);
@@ -2467,10 +2460,10 @@ __global__ void k_batch_states(const win_desc *wd, dev_state *out)
 // threads per workgroup for lag count L (what the walker's register rotation leaves of 512 registers per SIMD lane); 0 = none
 static int pipe_threads(int L)
 {
-    const int env = getenv("GH_PIPE_NT") ? atoi(getenv("GH_PIPE_NT")) : 0;      // (read on every call: the tests switch)
+    const int env = env_int("GH_PIPE_NT", 0);      // (read on every call: the tests switch)
     // (beyond ten lags the 512-thread form walks chunks of 11..14 positions and loses to the candidate pools on their own streams:
     // 20-25k against 31k haplotypes/s at 128 windows, scratch/pipe_lsweep.py; GH_PIPE_MAX_L=14 takes it all the same -- the tests)
-    const int max_l = getenv("GH_PIPE_MAX_L") ? atoi(getenv("GH_PIPE_MAX_L")) : 10;
+    const int max_l = env_int("GH_PIPE_MAX_L", 10);
     if (L < 2 || L > 14 || L > max_l) return 0;
     if (env == 512 || env == 768 || env == 1024) return env;
     return L <= 6 ? 1024 : (L <= 10 ? 768 : 512);
@@ -2481,51 +2474,34 @@ static int pipe_threads(int L)
 static bool pipe_spec_ok(const gh_handle *h)
 {
     const bool col = h->cfg.cond_mode == GH_COND_C || h->cfg.cond_mode == GH_COND_E;
-    const bool no_mt = getenv("GH_PIPE_MT") && atoi(getenv("GH_PIPE_MT")) == 0;
-    const bool no_col = getenv("GH_PIPE_COL") && atoi(getenv("GH_PIPE_COL")) == 0;
+    const bool no_mt = env_off("GH_PIPE_MT");
+    const bool no_col = env_off("GH_PIPE_COL");
     return !h->lt_full && !(col && no_col) && !(h->cfg.marginal_term && no_mt);
 }
 static int pipe_sweep_threads(int nt) { return nt == 1024 ? pipe_roles<1024>::NRW * 64 : (nt == 768 ? pipe_roles<768>::NRW * 64 : pipe_roles<512>::NRW * 64); }
 
-template <typename T, int LC, int NT>
+// the narrow launch, and for windows with a few five-candidate positions the WIDE one (k_wpipe<.., WIDE = true>, wpipe.hpp): the
+// default thread counts only
+template <typename T, bool WIDE, int LC, int NT>
 static hipError_t launch_wpipe_t(const pipe_params &P, const win_desc *d_wd, int n, size_t lds, hipStream_t st)
 {
-    hipError_t e = hipFuncSetAttribute((const void *)k_wpipe<T, LC, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute((const void *)k_wpipe<T, LC, NT, WIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_wpipe<T, LC, NT>), dim3(n), dim3(NT), lds, st, P, d_wd);
+    hipLaunchKernelGGL((k_wpipe<T, LC, NT, WIDE>), dim3(n), dim3(NT), lds, st, P, d_wd);
     return hipGetLastError();
 }
-template <typename T>
+template <typename T, bool WIDE>
 static hipError_t launch_wpipe(int L, int nt, const pipe_params &P, const win_desc *d_wd, int n, size_t lds, hipStream_t st)
 {
-#define GH_PIPE_CASE(l, t) case l: return launch_wpipe_t<T, l, t>(P, d_wd, n, lds, st);
+#define GH_PIPE_CASE(l, t) case l: return launch_wpipe_t<T, WIDE, l, t>(P, d_wd, n, lds, st);
     if (nt == 1024) {
         switch (L) { GH_PIPE_CASE(2, 1024) GH_PIPE_CASE(3, 1024) GH_PIPE_CASE(4, 1024) GH_PIPE_CASE(5, 1024) GH_PIPE_CASE(6, 1024) }
     } else if (nt == 768) {
-        switch (L) { GH_PIPE_CASE(5, 768) GH_PIPE_CASE(7, 768) GH_PIPE_CASE(8, 768) GH_PIPE_CASE(9, 768) GH_PIPE_CASE(10, 768) }
-    } else if (nt == 512) {
-        switch (L) { GH_PIPE_CASE(3, 512) GH_PIPE_CASE(5, 512) GH_PIPE_CASE(11, 512) GH_PIPE_CASE(12, 512) GH_PIPE_CASE(13, 512) GH_PIPE_CASE(14, 512) }
-    }
-#undef GH_PIPE_CASE
-    return hipErrorInvalidValue;
-}
-// ... and for windows with a few five-candidate positions (k_wpipe<.., WIDE = true>, wpipe.hpp): the default thread counts only
-template <typename T, int LC, int NT>
-static hipError_t launch_wpipe_w_t(const pipe_params &P, const win_desc *d_wd, int n, size_t lds, hipStream_t st)
-{
-    hipError_t e = hipFuncSetAttribute((const void *)k_wpipe<T, LC, NT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_wpipe<T, LC, NT, true>), dim3(n), dim3(NT), lds, st, P, d_wd);
-    return hipGetLastError();
-}
-template <typename T>
-static hipError_t launch_wpipe_w(int L, int nt, const pipe_params &P, const win_desc *d_wd, int n, size_t lds, hipStream_t st)
-{
-#define GH_PIPE_CASE(l, t) case l: return launch_wpipe_w_t<T, l, t>(P, d_wd, n, lds, st);
-    if (nt == 1024) {
-        switch (L) { GH_PIPE_CASE(2, 1024) GH_PIPE_CASE(3, 1024) GH_PIPE_CASE(4, 1024) GH_PIPE_CASE(5, 1024) GH_PIPE_CASE(6, 1024) }
-    } else if (nt == 768) {
+        if constexpr (!WIDE) { if (L == 5) return launch_wpipe_t<T, false, 5, 768>(P, d_wd, n, lds, st); }
         switch (L) { GH_PIPE_CASE(7, 768) GH_PIPE_CASE(8, 768) GH_PIPE_CASE(9, 768) GH_PIPE_CASE(10, 768) }
+    } else if constexpr (!WIDE) {
+        if (nt == 512)
+            switch (L) { GH_PIPE_CASE(3, 512) GH_PIPE_CASE(5, 512) GH_PIPE_CASE(11, 512) GH_PIPE_CASE(12, 512) GH_PIPE_CASE(13, 512) GH_PIPE_CASE(14, 512) }
     }
 #undef GH_PIPE_CASE
     return hipErrorInvalidValue;
@@ -2540,51 +2516,46 @@ static bool pipe_instantiated(int L, int nt)
     return false;
 }
 
-// the pipeline's preamble over the n windows whose descriptors stand at gwd, on `st`: marginals, snapshot and the full table of every
-// window.  N, W: the largest window's -- they size the grids; every kernel takes its window's own shape from the descriptor
+// what a spin over the n windows whose descriptors stand at gwd starts with, on `st`: the control words re-armed, marginals, snapshot.
+// N, W: the largest window's -- they size the grids; every kernel takes its window's own shape from the descriptor
+static void launch_preamble(const gh_handle *h0, hipStream_t st, const win_desc *gwd, int n, int N, int W)
+{
+    const unsigned marg_gx = (unsigned)(((N + 1) * 8 + 255) / 256);
+    marg_args m;
+    m.N = N; m.W = W; m.wd = gwd; m.sm = h0->sm; m.offer_zero = h0->cfg.offer_zero;
+    hipLaunchKernelGGL(k_rearm, dim3(n), dim3(64), 0, st, (dev_state *)nullptr, gwd, 0);
+    launch_marg<false>(h0, dim3(marg_gx, n), st, m);
+    hipLaunchKernelGGL(k_snapshot, dim3(marg_gx, n), dim3(256), 0, st, (double *)nullptr, (const double *)nullptr, N, gwd);
+}
+// the arguments of a batched k_lt over windows of up to N SNPs (every pointer from the descriptors)
+static lt_args batch_lt_args(const gh_handle *h0, const win_desc *gwd, int N, int W, int L)
+{
+    lt_args a;
+    a.N = N; a.W = W; a.L = L; a.cond_mode = h0->cfg.cond_mode; a.wd = gwd;
+    a.allow_ranked = walk_depth2_ok(h0->wmode == WM_SEG ? WM_SPEC : h0->wmode, L); a.sm = h0->sm;
+    return a;
+}
+// the pipeline's preamble: the above and the full table of every window
 static void pipe_preamble(const gh_handle *h0, hipStream_t st, const win_desc *gwd, int n, int N, int W, int L)
 {
-    const bool f64 = h0->cfg.storage == GH_STORAGE_F64;
-    const int bwm = h0->wmode == WM_SEG ? WM_SPEC : h0->wmode;
-    const unsigned marg_gx = (unsigned)(((N + 1) * 8 + 255) / 256);
     size_t lt_nb = ((size_t)(N + LT_PAD) * L * LT_BLK + 255) / 256;
     if (lt_nb > 4096) lt_nb = 4096;
-    hipLaunchKernelGGL(k_rearm, dim3(n), dim3(64), 0, st, (dev_state *)nullptr, gwd, 0);
-    if (f64) {
-        hipLaunchKernelGGL((k_marg<double, false>), dim3(marg_gx, n), dim3(256), 0, st, (double *)nullptr, N, W,
-                           (double *)nullptr, (double *)nullptr, (int32_t *)nullptr, (uint32_t *)nullptr, (double *)nullptr,
-                           (dev_state *)nullptr, gwd, (const uint8_t *)nullptr, 0.0, 0, (double *)nullptr, 0, (double *)nullptr, 0, 0, (const double *)nullptr, (gh_path_rec *)nullptr,
-                           h0->sm, h0->cfg.offer_zero, (double *)nullptr);
-        hipLaunchKernelGGL(k_snapshot, dim3(marg_gx, n), dim3(256), 0, st, (double *)nullptr, (const double *)nullptr, N, gwd);
-        // (the table WITHOUT the marginal term baked into its lag-1 entries: the pipeline's walker adds it itself)
-        hipLaunchKernelGGL(k_lt<double>, dim3((unsigned)lt_nb, n), dim3(256), 0, st, (const double *)nullptr, N, W, L,
-                           h0->cfg.cond_mode, 0, (const double *)nullptr, (const int32_t *)nullptr,
-                           (const uint32_t *)nullptr, (const double *)nullptr, (double *)nullptr, (dev_state *)nullptr,
-                           (const uint8_t *)nullptr, gwd, 0, walk_depth2_ok(bwm, L), (double *)nullptr, (double *)nullptr, h0->sm, (const double *)nullptr);
-    } else {
-        hipLaunchKernelGGL((k_marg<float, false>), dim3(marg_gx, n), dim3(256), 0, st, (float *)nullptr, N, W,
-                           (double *)nullptr, (double *)nullptr, (int32_t *)nullptr, (uint32_t *)nullptr, (double *)nullptr,
-                           (dev_state *)nullptr, gwd, (const uint8_t *)nullptr, 0.0, 0, (double *)nullptr, 0, (double *)nullptr, 0, 0, (const double *)nullptr, (gh_path_rec *)nullptr,
-                           h0->sm, h0->cfg.offer_zero, (double *)nullptr);
-        hipLaunchKernelGGL(k_snapshot, dim3(marg_gx, n), dim3(256), 0, st, (double *)nullptr, (const double *)nullptr, N, gwd);
-        hipLaunchKernelGGL(k_lt<float>, dim3((unsigned)lt_nb, n), dim3(256), 0, st, (const float *)nullptr, N, W, L,
-                           h0->cfg.cond_mode, 0, (const double *)nullptr, (const int32_t *)nullptr,
-                           (const uint32_t *)nullptr, (const double *)nullptr, (double *)nullptr, (dev_state *)nullptr,
-                           (const uint8_t *)nullptr, gwd, 0, walk_depth2_ok(bwm, L), (double *)nullptr, (double *)nullptr, h0->sm, (const float *)nullptr);
-    }
+    launch_preamble(h0, st, gwd, n, N, W);
+    // (the table WITHOUT the marginal term baked into its lag-1 entries: the pipeline's walker adds it itself)
+    launch_lt(h0, dim3((unsigned)lt_nb, n), st, batch_lt_args(h0, gwd, N, W, L));
 }
 // the pipeline's launch parameters for windows of up to N SNPs (C and the LDS: sized by the largest window) and their LDS bytes
 static pipe_params pipe_make_params(const gh_handle *h0, int N, int W, int L, int nt, bool wide, int max_paths, double min_remove, size_t *lds)
 {
-    const bool f64 = h0->cfg.storage == GH_STORAGE_F64;
+    const int es = (int)esize(h0);
     const int nr = pipe_sweep_threads(nt);
     pipe_params P;
     P.N = N; P.W = W; P.L = L; P.mt = h0->cfg.marginal_term ? 1 : 0; P.col = (h0->cfg.cond_mode == GH_COND_C || h0->cfg.cond_mode == GH_COND_E) ? 1 : 0;
-    P.C = wide ? pipe_chunk_w(N, L, nr, f64 ? 8 : 4, P.mt) : pipe_chunk(N, L, nr, f64 ? 8 : 4, P.mt);
+    P.C = wide ? pipe_chunk_w(N, L, nr, es, P.mt) : pipe_chunk(N, L, nr, es, P.mt);
     P.max_paths = max_paths; P.cond_mode = h0->cfg.cond_mode;
-    P.synth = getenv("GH_PIPE_SYNTH") ? (atoi(getenv("GH_PIPE_SYNTH")) != 0) : 1;          // (wpipe.hpp, the loaders: what it gains and costs)
+    P.synth = env_int("GH_PIPE_SYNTH", 1) != 0;          // (wpipe.hpp, the loaders: what it gains and costs)
     P.offer_zero = h0->cfg.offer_zero; P.prof = 0; P.min_remove = min_remove; P.sm = h0->sm;
-    *lds = wide ? pipe_lds_bytes_w(N, L, P.C, nr, f64 ? 8 : 4, P.mt) : pipe_lds_bytes(N, L, P.C, nr, f64 ? 8 : 4, P.mt);
+    *lds = wide ? pipe_lds_bytes_w(N, L, P.C, nr, es, P.mt) : pipe_lds_bytes(N, L, P.C, nr, es, P.mt);
     return P;
 }
 
@@ -2599,7 +2570,6 @@ static int batch_run_launches(gh_batch *b, const std::vector<win_desc> &wd, int 
     HIPCHK(hipStreamSynchronize(b->stream));        // wd is a host temporary
 
     gh_handle *h0 = b->hs[0];
-    const bool f64 = h0->cfg.storage == GH_STORAGE_F64;
     const int N = b->N, W = b->W, L = b->L;
     const int bwm = h0->wmode == WM_SEG ? WM_SPEC : h0->wmode;     // batched launches: one serial walker per window
     const unsigned marg_gx = (unsigned)(((N + 1) * 8 + 255) / 256);
@@ -2611,11 +2581,15 @@ static int batch_run_launches(gh_batch *b, const std::vector<win_desc> &wd, int 
     size_t lt_nb_inc = 64;                  // batched launches keep no walker tables: the steady-state k_lt only checks flags
     if (lt_nb_inc > 4096) lt_nb_inc = 4096;
     const bool inc_mode = lt_incremental_ok(h0);
+    // the fused reweight over the windows: path, partial sums and records from the descriptors
+    marg_args rw;
+    rw.N = N; rw.W = W; rw.use_state_ratio = 1; rw.G = inc_mode ? (double *)b->d_paths : nullptr;   // (non-null: take G from wd)
+    rw.L = L; rw.cond_mode = h0->cfg.cond_mode; rw.sm = h0->sm; rw.offer_zero = h0->cfg.offer_zero;
     // The windows go in up to three GROUPS, each on its own stream and one phase behind the group in front: a path is a
     // serial extension (one workgroup per window, 0.6 ms for 10k SNPs whatever the number of windows: latency) followed by
     // a reweight (HBM-bound, ~4 us per window).  In step, every group would wait out the extension with an idle memory
     // system and then share it; staggered, one group reweights while the others extend.
-    static const int groups_env = getenv("GH_BATCH_GROUPS") ? atoi(getenv("GH_BATCH_GROUPS")) : 0;
+    static const int groups_env = env_int("GH_BATCH_GROUPS", 0);
     int NG = groups_env > 0 ? groups_env : (n >= 96 ? 3 : (n >= 32 ? 2 : 1));
     if (NG > 3) NG = 3;
     if (NG > n) NG = n;
@@ -2642,47 +2616,19 @@ static int batch_run_launches(gh_batch *b, const std::vector<win_desc> &wd, int 
             if (s == 0) {
                 // (group g starts when group g-1 has finished its first extension)
                 if (g > 0) hipStreamWaitEvent(st, b->gevent[g - 1], 0);
-                hipLaunchKernelGGL(k_rearm, dim3(ng), dim3(64), 0, st, (dev_state *)nullptr, gwd, 0);
-                if (f64)
-                    hipLaunchKernelGGL((k_marg<double, false>), dim3(marg_gx, ng), dim3(256), 0, st, (double *)nullptr, N, W,
-                                       (double *)nullptr, (double *)nullptr, (int32_t *)nullptr, (uint32_t *)nullptr, (double *)nullptr,
-                                       (dev_state *)nullptr, gwd, (const uint8_t *)nullptr, 0.0, 0, (double *)nullptr, 0, (double *)nullptr, 0, 0, (const double *)nullptr, (gh_path_rec *)nullptr,
-                                       h0->sm, h0->cfg.offer_zero, (double *)nullptr);
-                else
-                    hipLaunchKernelGGL((k_marg<float, false>), dim3(marg_gx, ng), dim3(256), 0, st, (float *)nullptr, N, W,
-                                       (double *)nullptr, (double *)nullptr, (int32_t *)nullptr, (uint32_t *)nullptr, (double *)nullptr,
-                                       (dev_state *)nullptr, gwd, (const uint8_t *)nullptr, 0.0, 0, (double *)nullptr, 0, (double *)nullptr, 0, 0, (const double *)nullptr, (gh_path_rec *)nullptr,
-                                       h0->sm, h0->cfg.offer_zero, (double *)nullptr);
-                hipLaunchKernelGGL(k_snapshot, dim3(marg_gx, ng), dim3(256), 0, st, (double *)nullptr, (const double *)nullptr, N, gwd);
+                launch_preamble(h0, st, gwd, ng, N, W);
             }
-            if (f64)
-                hipLaunchKernelGGL(k_lt<double>, dim3((unsigned)(inc ? lt_nb_inc : lt_nb), ng), dim3(256), 0, st, (const double *)nullptr, N, W, L,
-                                   h0->cfg.cond_mode, h0->cfg.marginal_term, (const double *)nullptr, (const int32_t *)nullptr,
-                                   (const uint32_t *)nullptr, (const double *)nullptr, (double *)nullptr, (dev_state *)nullptr,
-                                   inc, gwd, s, walk_depth2_ok(bwm, L), (double *)nullptr, (double *)nullptr, h0->sm, (const double *)nullptr);
-            else
-                hipLaunchKernelGGL(k_lt<float>, dim3((unsigned)(inc ? lt_nb_inc : lt_nb), ng), dim3(256), 0, st, (const float *)nullptr, N, W, L,
-                                   h0->cfg.cond_mode, h0->cfg.marginal_term, (const double *)nullptr, (const int32_t *)nullptr,
-                                   (const uint32_t *)nullptr, (const double *)nullptr, (double *)nullptr, (dev_state *)nullptr,
-                                   inc, gwd, s, walk_depth2_ok(bwm, L), (double *)nullptr, (double *)nullptr, h0->sm, (const float *)nullptr);
+            lt_args la = batch_lt_args(h0, gwd, N, W, L);
+            la.bake_lm = h0->cfg.marginal_term; la.inc_path = inc; la.spin = s;
+            launch_lt(h0, dim3((unsigned)(inc ? lt_nb_inc : lt_nb), ng), st, la);
             const bool sample = g == 0 && b->prof_every > 0 && s > 0 && (s % b->prof_every) == 0;
             if (sample) { b->prof_windows = ng; pmark(0, st); }
             launch_walk_any(bwm, N, L, P, st, ng, gwd, s);
             if (sample) pmark(0, st);
             if (s == 0 && g + 1 < NG) hipEventRecord(b->gevent[g], st);
             if (sample) pmark(1, st);
-            if (f64)
-                hipLaunchKernelGGL((k_marg<double, true>), dim3(marg_gx, ng), dim3(256), 0, st, (double *)nullptr, N, W,
-                                   (double *)nullptr, (double *)nullptr, (int32_t *)nullptr, (uint32_t *)nullptr, (double *)nullptr,
-                                   (dev_state *)nullptr, gwd, (const uint8_t *)nullptr, 0.0, 1, (double *)nullptr, s,
-                                   inc_mode ? (double *)b->d_paths : (double *)nullptr, L, h0->cfg.cond_mode, (const double *)nullptr, (gh_path_rec *)nullptr,
-                                   h0->sm, h0->cfg.offer_zero, (double *)nullptr);   // non-null = take G from wd
-            else
-                hipLaunchKernelGGL((k_marg<float, true>), dim3(marg_gx, ng), dim3(256), 0, st, (float *)nullptr, N, W,
-                                   (double *)nullptr, (double *)nullptr, (int32_t *)nullptr, (uint32_t *)nullptr, (double *)nullptr,
-                                   (dev_state *)nullptr, gwd, (const uint8_t *)nullptr, 0.0, 1, (double *)nullptr, s,
-                                   inc_mode ? (double *)b->d_paths : (double *)nullptr, L, h0->cfg.cond_mode, (const double *)nullptr, (gh_path_rec *)nullptr,
-                                   h0->sm, h0->cfg.offer_zero, (double *)nullptr);   // non-null = take G from wd
+            rw.wd = gwd; rw.spin = s;
+            launch_marg<true>(h0, dim3(marg_gx, ng), st, rw);
             if (sample) pmark(1, st);
             hipLaunchKernelGGL(k_reweight_finish, dim3(ng), dim3(256), 0, st, (const double *)nullptr, (int)marg_gx,
                                (dev_state *)nullptr, 1, (gh_path_rec *)nullptr, gwd, s);
@@ -2696,11 +2642,8 @@ static int batch_run_launches(gh_batch *b, const std::vector<win_desc> &wd, int 
     HIPCHK(hipGetLastError());
     {
         // algorithmic bytes per window and launch (launch_walk / launch_reweight_marg use the same definitions)
-        const double es = f64 ? 8.0 : 4.0;
-        const int wl = W < L ? W : L;
-        b->prof_bytes[0] = (double)N * ((1.0 + (double)L) * CELL * es + 28.0);
-        b->prof_bytes[1] = (double)(N + 1) * ((double)W * 2.0 * es + 1.0 + CELL * es + 2 * 64 + 88 + 8) +
-                           (inc_mode ? (double)N * ((double)wl * 7 * es + (double)L * LT_ROW * 8.0) : 0.0);
+        b->prof_bytes[0] = walk_bytes(N, L, esize(h0));
+        b->prof_bytes[1] = reweight_bytes(N, W, L, esize(h0), inc_mode);
     }
     return GH_OK;
 }
@@ -2713,7 +2656,7 @@ static int batch_spin_on_streams(gh_batch *b, const std::vector<std::pair<int, i
 {
     const int nj = (int)jobs.size();
     if (nj == 0) return GH_OK;
-    static const int nthr_env = getenv("GH_BATCH_THREADS") ? atoi(getenv("GH_BATCH_THREADS")) : 8;
+    static const int nthr_env = env_int("GH_BATCH_THREADS", 8);
     const int nthr = nthr_env < 1 ? 1 : (nthr_env > nj ? nj : nthr_env);
     std::vector<int> rcs(nj, GH_OK);
     std::vector<std::string> errs(nj);
@@ -2839,14 +2782,9 @@ static int pipe_buffers(gh_batch *b, gh_handle *h)
     }
     if (h->cfg.marginal_term && !h->pipe_lm) HIPCHK(hipMalloc((void **)&h->pipe_lm, sizeof(double) * 4 * ((size_t)h->N + 2)));
     if (h->cfg.cond_mode == GH_COND_C || h->cfg.cond_mode == GH_COND_E) {
-        const size_t nel = h->n_cells * CELL;
-        if (!h->tband && hipMalloc(&h->tband, nel * esize(h)) != hipSuccess) { h->tband = nullptr; return fail(GH_ERR_NOMEM, "hipMalloc for the to-major band failed"); }
-        if (h->tband_epoch != h->band_epoch) {
-            const unsigned nbt = (unsigned)((nel + 255) / 256);
-            if (h->cfg.storage == GH_STORAGE_F64) hipLaunchKernelGGL(k_band_to_major<double>, dim3(nbt), dim3(256), 0, b->stream, (const double *)h->band, (double *)h->tband, nel, h->W);
-            else hipLaunchKernelGGL(k_band_to_major<float>, dim3(nbt), dim3(256), 0, b->stream, (const float *)h->band, (float *)h->tband, nel, h->W);
-            h->tband_epoch = h->band_epoch;
-        }
+        int rc = ensure_tband(h, b->stream);
+        if (rc) return rc;
+        h->tband_epoch = h->band_epoch;
     }
     return GH_OK;
 }
@@ -2863,10 +2801,10 @@ struct pipe_group { int L, nt, N, W; std::vector<int> ws; };
 static std::vector<pipe_group> pipe_groups(gh_batch *b, std::vector<int> &left)
 {
     const gh_handle *h0 = b->hs[0];
-    const int pipe_env = getenv("GH_PIPE") ? atoi(getenv("GH_PIPE")) : 1;
-    const int pipe_min = getenv("GH_PIPE_MIN") ? atoi(getenv("GH_PIPE_MIN")) : 24;
+    const int pipe_env = env_int("GH_PIPE", 1);
+    const int pipe_min = env_int("GH_PIPE_MIN", 24);
     const int bwm0 = h0->wmode == WM_SEG ? WM_SPEC : h0->wmode;
-    const int es = h0->cfg.storage == GH_STORAGE_F64 ? 8 : 4, mt = h0->cfg.marginal_term ? 1 : 0;
+    const int es = (int)esize(h0), mt = h0->cfg.marginal_term ? 1 : 0;
     b->pipe_windows = b->pipe_aborted = b->pinfo_nt = b->pinfo_c = 0;
     std::map<int, std::vector<int>> byL;
     for (int w = 0; w < b->n; w++) byL[b->hs[w]->L].push_back(w);
@@ -2903,9 +2841,8 @@ static int pipe_spin_groups(gh_batch *b, const std::vector<pipe_group> &groups, 
 {
     const int n = b->n;
     gh_handle *h0 = b->hs[0];
-    const bool f64 = h0->cfg.storage == GH_STORAGE_F64;
-    const int es = f64 ? 8 : 4, mt = h0->cfg.marginal_term ? 1 : 0;
-    const bool wide_env = !(getenv("GH_PIPE_WIDE") && atoi(getenv("GH_PIPE_WIDE")) == 0);
+    const int es = (int)esize(h0), mt = h0->cfg.marginal_term ? 1 : 0;
+    const bool wide_env = !env_off("GH_PIPE_WIDE");
     int rc;
     for (int g = 0; g < 3; g++)
         if (!b->gstream[g]) HIPCHK(hipStreamCreateWithFlags(&b->gstream[g], hipStreamNonBlocking));
@@ -2987,9 +2924,10 @@ static int pipe_spin_groups(gh_batch *b, const std::vector<pipe_group> &groups, 
         if (mark) P.prof = (b->prof_every > 0 || getenv("GH_PIPE_STAMPS")) ? 1 : 0;
         if (mark && b->prof_every > 0) { b->prof_windows = q.cnt; pmark(st); }
         const win_desc *gwd = b->d_wd + q.off;
-        hipError_t le;
-        if (q.wide) le = f64 ? launch_wpipe_w<double>(g.L, g.nt, P, gwd, q.cnt, lds, st) : launch_wpipe_w<float>(g.L, g.nt, P, gwd, q.cnt, lds, st);
-        else le = f64 ? launch_wpipe<double>(g.L, g.nt, P, gwd, q.cnt, lds, st) : launch_wpipe<float>(g.L, g.nt, P, gwd, q.cnt, lds, st);
+        const hipError_t le = with_storage(h0, [&](auto z) {
+            using T = decltype(z);
+            return q.wide ? launch_wpipe<T, true>(g.L, g.nt, P, gwd, q.cnt, lds, st) : launch_wpipe<T, false>(g.L, g.nt, P, gwd, q.cnt, lds, st);
+        });
         if (le != hipSuccess)
             return fail(GH_ERR_HIP, "%s: the %s pipeline launch failed (L=%d, %d threads, %zu bytes of LDS): %s", phase.who, q.wide ? "wide" : "narrow",
                         g.L, g.nt, lds, hipGetErrorString(le));
@@ -3092,7 +3030,7 @@ extern "C" int gh_batch_spin(gh_batch_t *b, int max_paths, double min_remove, ui
     // (measured on C3, MI355X: 8 windows 37k haplotypes/s this way against ~16k batched; 32 windows 45k either way -- the
     // chip is then busy with k_seg; from 48 windows on the batched serial walkers, one workgroup per window, win: 114k at 256)
     // (read on every call: the tests switch between the two ways; -1 = always the batched kernels)
-    const int batch_cut = getenv("GH_BATCH_STREAMS_MAX") ? atoi(getenv("GH_BATCH_STREAMS_MAX")) : 47;
+    const int batch_cut = env_int("GH_BATCH_STREAMS_MAX", 47);
     const bool seg = seg_ok(b->hs[0]->wmode, b->L), cw = cw_ok(b->hs[0]->wmode, b->L);
     std::vector<int> rest;                      // windows no pipeline group takes, then those it leaves PIPE_NOT_STARTED
     const std::vector<pipe_group> groups = pipe_groups(b, rest);
@@ -3232,10 +3170,10 @@ extern "C" int gh_export_band(gh_t *h, double *out)
     double *d = nullptr;
     HIPCHK(hipMalloc((void **)&d, n * sizeof(double)));
     const unsigned nb = (unsigned)((n + 255) / 256);
-    if (h->cfg.storage == GH_STORAGE_F64)
-        hipLaunchKernelGGL(k_export<double>, dim3(nb), dim3(256), 0, h->stream, (const double *)h->band, d, n, h->W);
-    else
-        hipLaunchKernelGGL(k_export<float>, dim3(nb), dim3(256), 0, h->stream, (const float *)h->band, d, n, h->W);
+    with_storage(h, [&](auto z) {
+        using T = decltype(z);
+        hipLaunchKernelGGL(k_export<T>, dim3(nb), dim3(256), 0, h->stream, (const T *)h->band, d, n, h->W);
+    });
     hipError_t e = hipMemcpyAsync(out, d, n * sizeof(double), hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     hipFree(d);
@@ -3252,10 +3190,10 @@ extern "C" int gh_import_band(gh_t *h, const double *in)
     HIPCHK(hipMalloc((void **)&d, n * sizeof(double)));
     hipError_t e = hipMemcpyAsync(d, in, n * sizeof(double), hipMemcpyHostToDevice, h->stream);
     const unsigned nb = (unsigned)((n + 255) / 256);
-    if (h->cfg.storage == GH_STORAGE_F64)
-        hipLaunchKernelGGL(k_import<double>, dim3(nb), dim3(256), 0, h->stream, (double *)h->band, d, n, h->W);
-    else
-        hipLaunchKernelGGL(k_import<float>, dim3(nb), dim3(256), 0, h->stream, (float *)h->band, d, n, h->W);
+    with_storage(h, [&](auto z) {
+        using T = decltype(z);
+        hipLaunchKernelGGL(k_import<T>, dim3(nb), dim3(256), 0, h->stream, (T *)h->band, d, n, h->W);
+    });
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     hipFree(d);
     h->dirty_marg = h->dirty_lt = true; h->lt_inc_path = nullptr; h->band_zero = false; h->band_epoch++;
@@ -3407,8 +3345,8 @@ extern "C" int gh_debug_walk_clock(gh_t *h, uint64_t out[4])
     if (!h || !out) return fail(GH_ERR_ARG, "null argument");
     if (set_dev(h)) return GH_ERR_HIP;
     dev_state hs;
-    HIPCHK(hipMemcpyAsync(&hs, h->dstate, sizeof hs, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    int rc = read_state(h, &hs);
+    if (rc) return rc;
     out[0] = hs.dbg[0]; out[1] = hs.dbg[1]; out[2] = hs.dbg[2]; out[3] = hs.dbg[3];
     if (out[3] == 3) {
         // out[1]: the state space the extension walked -- 4 ranks, 5 symbols, 6 mixed radix (seg_class, from the same control words);
