@@ -54,6 +54,12 @@ class gh_assign_stats(C.Structure):
                 ("n_unexplained", C.c_int64)]
 
 
+class gh_score_rec(C.Structure):
+    _fields_ = [("ll_chain", C.c_double), ("hp_current", C.c_double), ("hp_original", C.c_double), ("min_marginal", C.c_double),
+                ("min_margin", C.c_double), ("n_on", C.c_int32), ("n_greedy", C.c_int32), ("first_off", C.c_int32),
+                ("argmin_margin", C.c_int32)]
+
+
 _lib = None
 
 
@@ -126,6 +132,7 @@ def load():
         "gh_debug_walk_clock": [vp, vp],
         "gh_debug_pool_geometry": [i32, i32, i32, vp],
         "gh_assign_reads": [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, P(gh_assign_stats)],
+        "gh_score_paths": [vp, vp, i32, vp, vp, vp, vp],
         "gh_coverage_sites": [i32, vp, vp, vp, i64, C.c_int32, C.c_int32, C.c_int32, vp, vp],
     }
     for name, args in sigs.items():

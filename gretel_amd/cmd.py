@@ -11,6 +11,12 @@ Files written (formats: docs/protocol.rst:48-77):
 and, with --assign-reads (no reference counterpart; INTEGRATION.md "Read assignment"):
     <out>/gretel.support  "# n_reads n_informative n_unique n_ambiguous n_unexplained" + one line per haplotype:
                           i_0, unique, shared, mismatches, unique / n_unique
+
+and, with --score-paths / --known FASTA (INTEGRATION.md "Scoring haplotypes"), against the matrix as it was before any reweighting:
+    <out>/gretel.scores   "# N L cond_mode marginal_term" + one line per recovered haplotype: i_0, ll_chain, hp_original, n_greedy,
+                          n_on, first_off, min_margin, argmin_margin and the genomic position of argmin_margin
+    <out>/gretel.known    the same per record of FASTA (its name for i_0), then the i_0 of the nearest recovered haplotype and the
+                          number of SNPs at which they differ
 """
 from __future__ import annotations
 
@@ -47,6 +53,7 @@ def build_parser():
     p.add_argument("--dumpsnps", type=str, default=None, help="dump the SNP positions to this path")
     p.add_argument("--pepper", action="store_true", help="permissive read filter (pysam stepper 'all' in the reference)")
     add_assign_options(p)
+    add_score_options(p)
     p.add_argument("--version", action="version", version="%(prog)s " + __version__)
     return p
 
@@ -59,6 +66,14 @@ def add_assign_options(p):
                    "out as uninformative [default: 2]")
     p.add_argument("--max-mismatch", type=int, default=-1, help="with --assign-reads: reads whose best haplotype differs at more "
                    "SNPs are unexplained (-1 = no limit) [default: -1]")
+
+
+def add_score_options(p):
+    """--score-paths and --known: haplotypes scored against the matrix as the reads filled it."""
+    p.add_argument("--score-paths", action="store_true", help="score every recovered haplotype against the unreweighted matrix "
+                   "(chain likelihood, per-SNP margins) and write gretel.scores")
+    p.add_argument("--known", metavar="FASTA", default=None, help="score the haplotypes of FASTA (sequences in the contig's "
+                   "coordinates, as --master) against the unreweighted matrix and write gretel.known")
 
 
 def read_first_fasta_record(path):
@@ -239,6 +254,73 @@ def write_support(paths, hansel, args):
         fh.write(support_text([paths[k]["i_0"] for k in keys], res))
 
 
+def _path_array(paths, keys, n):
+    import numpy as np
+    return np.array([[s.i for s in paths[k]["hansel_path"]] for k in keys], dtype=np.uint8).reshape(len(keys), n + 1)
+
+
+def scores_text(head, names, res, snp_rev, nearest=None):
+    """gretel.scores / gretel.known: "# N L cond_mode marginal_term" (`head`), then per haplotype (in the order of `names`: i_0s
+    or record names) its name, ll_chain, hp_original, n_greedy, n_on, first_off, min_margin, argmin_margin and the genomic
+    position of argmin_margin (0 where there is none); `res` is Hansel.score_paths' dict.  nearest (gretel.known): per
+    haplotype the (i_0, differing SNPs) of the nearest recovered haplotype, two more columns."""
+    lines = ["# %d\t%d\t%s\t%d\n" % tuple(head)]
+    for q, name in enumerate(names):
+        arg = int(res["argmin_margin"][q])
+        line = "%s\t%.6f\t%.6f\t%d\t%d\t%d\t%.6f\t%d\t%d" % (
+            name, res["ll_chain"][q], res["hp_original"][q], int(res["n_greedy"][q]), int(res["n_on"][q]), int(res["first_off"][q]),
+            res["min_margin"][q], arg, snp_rev[arg - 1] if arg > 0 else 0)
+        if nearest is not None:
+            line += "\t%d\t%d" % tuple(nearest[q])
+        lines.append(line + "\n")
+    return "".join(lines)
+
+
+def nearest_recovered(known, recovered, i0s):
+    """Per row of `known` the (i_0, differing SNPs) of the row of `recovered` that differs from it at the fewest SNP columns; the
+    lowest i_0 wins a tie (`i0s` ascend); (-1, -1) when nothing was recovered."""
+    import numpy as np
+    if len(recovered) == 0:
+        return [(-1, -1)] * len(known)
+    d = (np.asarray(known)[:, None, 1:] != np.asarray(recovered)[None, :, 1:]).sum(axis=2)
+    best = d.argmin(axis=1)
+    return [(int(i0s[b]), int(d[q, b])) for q, b in enumerate(best)]
+
+
+def _score_head(unweighted, vcf_h):
+    return (vcf_h["N"], unweighted.L, unweighted._cfg["cond_mode"], int(unweighted._cfg["marginal_term"]))
+
+
+def write_scores(paths, unweighted, vcf_h, args):
+    """--score-paths: the distinct haplotypes in out.fasta's order (by i_0) against the copy taken before the spins."""
+    keys = sorted(paths, key=lambda x: paths[x]["i_0"])
+    res = unweighted.score_paths(_path_array(paths, keys, unweighted.n))
+    with open(args.out + "/gretel.scores", "w") as fh:
+        fh.write(scores_text(_score_head(unweighted, vcf_h), [paths[k]["i_0"] for k in keys], res, vcf_h["snp_rev"]))
+
+
+def write_known(paths, unweighted, vcf_h, args):
+    """--known: every record of the FASTA against the same copy, and the recovered haplotype nearest to it."""
+    keys = sorted(paths, key=lambda x: paths[x]["i_0"])
+    names, known = util.known_snp_paths(args.known, vcf_h, unweighted)
+    res = unweighted.score_paths(known)
+    near = nearest_recovered(known, _path_array(paths, keys, unweighted.n), [paths[k]["i_0"] for k in keys])
+    with open(args.out + "/gretel.known", "w") as fh:
+        fh.write(scores_text(_score_head(unweighted, vcf_h), names, res, vcf_h["snp_rev"], nearest=near))
+
+
+def check_score_options(args):
+    """The refusal of --known (before any BAM read or GPU call): a message, or None."""
+    if args.known is None:
+        return None
+    try:
+        if not util.read_fasta_records(args.known):
+            return "--known %s holds no FASTA record" % args.known
+    except OSError as e:
+        return "--known %s cannot be read: %s" % (args.known, e.strerror)
+    return None
+
+
 def check_assign_options(args):
     """The refusals of --min-snps / --max-mismatch (before any BAM read or GPU call): a message, or None."""
     if args.assign_reads and args.min_snps < 1:
@@ -250,7 +332,7 @@ def check_assign_options(args):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    bad = check_assign_options(args)
+    bad = check_assign_options(args) or check_score_options(args)
     if bad:
         sys.stderr.write("[FAIL] %s\n" % bad)
         return 2
@@ -276,6 +358,8 @@ def main(argv=None):
                                 debug_reads=debug_reads, debug_pos=debug_pos, max_depth=args.max_depth,
                                 stepper="all" if args.pepper else "samtools", keep_reads=args.assign_reads)     # cmd.py:78
     hansel.snapshot_original()                                                    # cmd.py:79 (what the copy is used for)
+    # (the reference's copy of cmd.py:79, made only where something is scored against the matrix as the reads filled it)
+    unweighted = hansel.copy() if (args.score_paths or args.known) else None
     if args.dumpmatrix:
         hansel.save_hansel_dump(args.dumpmatrix)                                  # cmd.py:81-82
     if gap_report(hansel, vcf_h):
@@ -295,6 +379,10 @@ def main(argv=None):
     write_outputs(paths, hansel, vcf_h, args)
     if args.assign_reads:
         write_support(paths, hansel, args)
+    if args.score_paths:
+        write_scores(paths, unweighted, vcf_h, args)
+    if args.known:
+        write_known(paths, unweighted, vcf_h, args)
     try:                        # the decoder's kept working buffers (include/gretel_io.h: GIO_KEEP_MB): a run has one decode
         from . import bamio
         if getattr(bamio, "_io", None) is not None:

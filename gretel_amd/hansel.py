@@ -30,6 +30,7 @@ from ._lib import check
 SYMBOLS = ['A', 'C', 'G', 'T', 'N', '-', '_']
 UNSYMBOLS = ['N', '_']
 _SYM_LUT = np.frombuffer("".join(SYMBOLS).encode(), dtype=np.uint8)
+SCORE_REC = np.dtype(_lib.gh_score_rec)       # gh_score_rec as a numpy record: five float64, four int32
 
 
 class HanselSymbol:
@@ -327,6 +328,28 @@ class Hansel:
                                         _p(mism), rp[0], rp[1], rp[2], C.byref(st)))
         out.update(unique=unique, shared=shared, mismatches=mism, n_reads=int(st.n_reads), n_informative=int(st.n_informative),
                    n_unique=int(st.n_unique), n_ambiguous=int(st.n_ambiguous), n_unexplained=int(st.n_unexplained))
+        return out
+
+    def score_paths(self, paths, per_position=False):
+        """How the haplotypes `paths` (uint8[H][N+1] symbol indices: rows of spin()'s paths; one path may come as uint8[N+1])
+        stand against the tensor as it is now (gh_score_paths; the definition: INTEGRATION.md "Scoring haplotypes").  Returns a
+        dict of arrays with one entry per haplotype: ll_chain, hp_current, hp_original, min_marginal, min_margin (float64),
+        n_on, n_greedy, first_off, argmin_margin (int32); with per_position also weight, margin (float64[H][N+1]) and pick
+        (uint8[H][N+1]).  The tensor is not touched."""
+        self._ensure()
+        p = np.ascontiguousarray(paths, dtype=np.uint8)
+        if p.ndim == 1:
+            p = p.reshape(1, -1) if p.size else p.reshape(0, self.n + 1)
+        if p.ndim != 2 or p.shape[1] != self.n + 1:
+            raise ValueError("paths must be uint8[H][N+1] with N+1 = %d (got shape %s)" % (self.n + 1, p.shape))
+        H = p.shape[0]
+        recs = np.zeros(H, dtype=SCORE_REC)
+        out = {}
+        if per_position:
+            out = dict(weight=np.zeros(p.shape), margin=np.zeros(p.shape), pick=np.zeros(p.shape, dtype=np.uint8))
+        pp = [_p(out[k]) if per_position else None for k in ("weight", "margin", "pick")]
+        check(self._lib.gh_score_paths(self._h, _p(p), H, _p(recs), pp[0], pp[1], pp[2]))
+        out.update((k, recs[k].copy()) for k in SCORE_REC.names)
         return out
 
     def clear(self):

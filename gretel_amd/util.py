@@ -429,3 +429,43 @@ def load_from_bam(bam_path, target_contig, start_pos, end_pos, vcf_handler, use_
         raise ZeroDivisionError("no read carries more than one SNP (gretel/util.py:333 divides by n_reads)")
     sys.stderr.write("[NOTE] Setting Gretel.L to %d\n" % hansel.L)                                    # util.py:334
     return hansel
+
+
+# ---------------------------------------------------------------------------------------------
+# known haplotypes
+# ---------------------------------------------------------------------------------------------
+def read_fasta_records(path):
+    """(name, sequence) of every record of a FASTA file; the name is the header up to the first blank."""
+    recs = []
+    with open(path) as fh:
+        for line in fh:
+            if line.startswith(">"):
+                head = line[1:].split()
+                recs.append([head[0] if head else "", []])
+            elif recs:
+                recs[-1][1].append(line.strip())
+    return [(name, "".join(parts)) for name, parts in recs]
+
+
+def known_snp_paths(fasta_path, vcf_h, hansel):
+    """gretel/gretel.py:11 ("TODO Util to parse known input and return SNP seq"): every record of a FASTA whose sequences are in
+    the contig's coordinates (the convention of --master: base q of a record is position q + 1 of the contig) as a path over the
+    window's SNPs -- its base at every vcf_h["snp_rev"] position as a symbol index of `hansel`, '_' in front.  Lower case is
+    folded, '-' is the deletion symbol; anything else, and a position beyond the record's end, is N.  Returns (names,
+    uint8[K][N+1]): rows for Hansel.score_paths.  ValueError for a file without records."""
+    recs = read_fasta_records(fasta_path)
+    if not recs:
+        raise ValueError("%s holds no FASTA record" % fasta_path)
+    n = vcf_h["N"]
+    lut = np.full(256, hansel.symbols_d["N"].i, dtype=np.uint8)
+    for c in "ACGT-":
+        lut[ord(c)] = hansel.symbols_d[c].i
+        lut[ord(c.lower())] = hansel.symbols_d[c].i
+    pos0 = np.array([vcf_h["snp_rev"][j] - 1 for j in range(n)], dtype=np.int64)
+    paths = np.full((len(recs), n + 1), hansel.symbols_d["N"].i, dtype=np.uint8)
+    paths[:, 0] = hansel.symbols_d["_"].i
+    for k, (_, seq) in enumerate(recs):
+        raw = np.frombuffer(seq.encode("latin-1", "replace"), dtype=np.uint8)
+        inside = pos0 < len(raw)
+        paths[k, 1:][inside] = lut[raw[pos0[inside]]]
+    return [name for name, _ in recs], paths

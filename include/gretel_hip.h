@@ -244,6 +244,34 @@ int gh_assign_reads(gh_t *h, const gh_reads_t *reads, const uint8_t *paths, int 
                     int32_t *read_hap, int32_t *read_best, int32_t *read_informative,
                     gh_assign_stats *stats);
 
+/* Scoring given haplotypes (gretel/gretel.py:11 "TODO Util to parse known input and return SNP seq" is as far as the reference
+ * goes; INTEGRATION.md "Scoring haplotypes").  paths = [n_paths][N + 1] symbol indices, rows as gh_spin writes them (index 0,
+ * the '_' sentinel, is ignored: the history reads '_' there).  With L, the conditional, the marginal term, the candidate order and
+ * offer_zero of the handle, at every position p = 1..N of a path x: cm(p) and w_p[s] are what gh_edge_weights_at(h, p, x, ...)
+ * returns -- the history is x's own, any symbol 0..6 may sit in it; pick(p) is the candidate gh_generate_path would take (the
+ * first of cand_order, replaced only by a strictly larger weight; 255 when cm(p) is empty).  p is ON when x[p] is in cm(p): then
+ * weight(p) = w_p[x[p]] and margin(p) = weight(p) - max of the other candidates' weights (+inf when there is none; > 0: the walk
+ * follows the path here, < 0: it leaves it, 0: a tie, which cand_order decides).  OFF (x[p] is N, '_', an allele not offered
+ * at p, or p is a hole): weight(p) = margin(p) = -inf.  Per path, over the ON positions only, in ascending p, as sequential
+ * binary64 additions from 0.0 (the order of gretel/gretel.py:185-186): ll_chain = sum of weight(p) -- the quantity the walk
+ * maximises step by step; hp_current = sum of log10 marginal(x[p], p); hp_original = the same under the snapshot of
+ * gh_snapshot_original (the current marginals when none was taken); min_marginal = the smallest current marginal (+inf when
+ * nothing is on); min_margin / argmin_margin = the smallest margin and the first position that has it (+inf / 0 when nothing is
+ * on); n_on; n_greedy = on positions with x[p] == pick(p); first_off = the first off position
+ * (0: none).  Scoring the path of gh_generate_path on the tensor it came from gives n_greedy == n_on == N, every margin >= 0 and
+ * its hp_current, hp_original and min_marginal bit for bit.
+ * recs: [n_paths]; weight / margin / pick: [n_paths][N + 1], each may be NULL; pick[.][0] = 6, weight[.][0] = margin[.][0] = 0.
+ * GH_ERR_ARG for a null h, paths or recs or n_paths < 0; n_paths == 0 returns GH_OK and writes nothing; GH_ERR_SYMBOL for a path
+ * byte above 6; GH_ERR_STATE before any fill, add or import.  Reads the tensor only: the band, L, the fill statistics, the
+ * snapshot and the results of a following gh_spin stay as they are.  The device scratch is bounded whatever n_paths is (the paths
+ * go through in slabs). */
+typedef struct {
+    double ll_chain, hp_current, hp_original, min_marginal, min_margin;
+    int32_t n_on, n_greedy, first_off, argmin_margin;
+} gh_score_rec;
+int gh_score_paths(gh_t *h, const uint8_t *paths, int n_paths, gh_score_rec *recs,
+                   double *weight, double *margin, uint8_t *pick);
+
 /* tensor export/import for --dumpmatrix (gretel/cmd.py:81-82) and tests:
  * band layout [(N+2)][band][7][7] as doubles; dense layout [7][7][N+2][N+2] (gretel/cmd.py:76-77). */
 int gh_export_band(gh_t *h, double *out);
