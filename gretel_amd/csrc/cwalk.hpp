@@ -153,12 +153,17 @@ struct cw_params {
     cw_key key0;              // key of the start state (0 in the packed mode)
 };
 
-__device__ __forceinline__ cw_key cw_hash_digits(const uint8_t *d, int L)
+// the hash of a state kept as bytes: FNV-1a over its picks, lag 1 first (cw_hash_step per pick, from CW_HASH_SEED), then a finisher
+#define CW_HASH_SEED 0xcbf29ce484222325ull
+__host__ __device__ __forceinline__ cw_key cw_hash_step(cw_key h, unsigned d) { h ^= d; return h * 0x100000001b3ull; }
+__host__ __device__ __forceinline__ cw_key cw_hash_finish(cw_key h) { h ^= h >> 32; h *= 0x9e3779b97f4a7c15ull; h ^= h >> 29; return h; }
+// digit(l) = the pick of lag l, l = 1 .. L
+template <typename D>
+__host__ __device__ __forceinline__ cw_key cw_hash_digits(D &&digit, int L)
 {
-    unsigned long long h = 0xcbf29ce484222325ull;
-    for (int l = 0; l < L; l++) { h ^= d[l]; h *= 0x100000001b3ull; }
-    h ^= h >> 32; h *= 0x9e3779b97f4a7c15ull; h ^= h >> 29;
-    return h;
+    cw_key h = CW_HASH_SEED;
+    for (int l = 1; l <= L; l++) h = cw_hash_step(h, digit(l));
+    return cw_hash_finish(h);
 }
 // (states lie LD = L rounded up to 4 bytes apart in 4-byte-aligned arrays: compared as words, every load on its way before the
 // first comparison -- byte by byte with an early exit it was a chain of up to L dependent loads, 15-30 us of k_clink at 33-48 lags;
@@ -175,32 +180,172 @@ __device__ __forceinline__ bool cw_same_digits(const uint8_t *a, const uint8_t *
 }
 
 // -------------------------------------------------------------------------------------------------------------
+// What the three pool walkers share -- k_cwalk (a state packed in 64 bits), k_cwalkg (a state as bytes next to its hash, the lag
+// count known at run time) and k_cwalk2 (k_cwalkg's states with k_cwalk's step) -- stated once.  A kernel keeps its step to itself
+// (how the terms are read, how the state is carried), and the loops whose shape the register allocation of its step hangs on:
+// the merge of the pending list around cw_evict, and what follows a segment (exit, request, run-on).  Moved behind a call, each
+// of those cost some instantiation registers or spills, though the instructions are the same.
+// -------------------------------------------------------------------------------------------------------------
+// The gate at a walker's entry; false where the kernel returns.
+template <int R>
+__device__ __forceinline__ bool cw_enter(const cw_params &P)
+{
+    dev_state *st = P.st;
+    const dev_ctl c = load_ctl(st);
+    if (c.stop || c.lt_stale || c.cw_unres) return false;
+    if (P.round > 0 && c.cw_open_at < 0) return false;      // the chain closed in an earlier round
+    if (P.check_masks == 2 || (P.check_masks && c.cm_same == 0)) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) st->lt_stale = 1;
+        return false;
+    }
+    if ((c.ranked != 0) != (R == 4)) {                      // the table is not in this instantiation's layout (it was rebuilt): the host looks again
+        if (blockIdx.x == 0 && threadIdx.x == 0) st->cw_unres = 2;
+        return false;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        st->cur_hole = c.first_hole;      // (the flags stand until k_cemit re-arms them)
+        if (P.round == 0) st->cw_open_at = 0;           // a new path: its chain is open until a k_cscan says otherwise (round 0's may be skipped)
+    }
+    return true;
+}
+
+// A full pool gives up the entry that was on a chain longest ago (the lowest index among equals), never the start state and
+// never one of this path.  Called by the pool's first wavefront, lane = entry, lh = the pool's last_hit; -1: every entry was
+// on a chain of this path (cannot happen: one per path).
+__device__ __forceinline__ int cw_evict(const cw_params &P, const int32_t *lh, int s, int tid)
+{
+    int mine = (tid == 0 && s == 0) ? 0x7fffffff : lh[tid], who = tid;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const int om = __shfl_xor(mine, o), ow = __shfl_xor(who, o);
+        if (om < mine || (om == mine && ow < who)) { mine = om; who = ow; }
+    }
+    return mine >= P.stamp ? -1 : who;
+}
+
+// The slice of G a chunk of targets needs, on its way to LDS through registers: for target t = c0 + 1 + tl and lag l the rows
+// of source t - l at that lag -- a run of COLS doubles per (tl, l, row) in G ([i][row][lag][col]), copied as a unit.  Position 0
+// carries '_' whatever the digit says (row 5), positions in front of it add +0.0, and so do the blocks of lags beyond L where an
+// instantiation for LC lags serves fewer (k_cwalk2).  The loads of chunk k+1 are issued before chunk k is walked and stay in
+// registers under the walk: their latency is off the critical path.  (Two functions over the kernel's plain arrays, each called
+// through a lambda of the kernel: called directly, hipcc kept the arrays as one vector value -- 30 registers at 6 lags over the
+// symbols; in a struct handed to a lambda it moved them to scratch memory, docs/HISTORY.md, round 6.)
+template <int R, int LC, int CH>
+struct cw_slice {
+    static constexpr int ROWS = cw_rows(R), COLS = cw_cols(R), ENT = ROWS * COLS, NTHR = CW_K * cw_lanes(R);
+    static constexpr int NV = (CH * LC * ROWS + NTHR - 1) / NTHR;
+    // marginal term: the log-marginals of the chunk's targets (column b: rank or symbol, like G's columns), fetched with the
+    // slice, added in front of the lag-1 entries once the slice stands in LDS
+    static constexpr int NLM = (CH * LT_ROW + NTHR - 1) / NTHR;
+
+    // nc targets from c0 + 1 on, at L <= LC lags (the row stride of G)
+    static __device__ __forceinline__ void fetch(const cw_params &P, int L, int tid, int c0, int nc, double (&pre)[NV][COLS], double (&prelm)[NLM])
+    {
+        if (P.mt) {
+#pragma unroll
+            for (int k = 0; k < NLM; k++) {
+                const int e = tid + k * NTHR;
+                const int tl = e / LT_ROW, bb = e - tl * LT_ROW;
+                const int tgt = c0 + 1 + tl;
+                prelm[k] = 0.0;
+                if (tl < nc && bb < R) prelm[k] = R == 4 ? P.rinfo[(size_t)tgt * RINFO + bb] : P.minfo[(size_t)tgt * MINFO + bb];
+            }
+        }
+        const int total = nc * LC * ROWS;
+#pragma unroll
+        for (int k = 0; k < NV; k++) {
+            const int u = tid + k * NTHR;
+#pragma unroll
+            for (int cc = 0; cc < COLS; cc++) pre[k][cc] = 0.0;
+            if (u < total) {
+                const int row = u % ROWS, l1 = (u / ROWS) % LC, tl = u / (ROWS * LC);
+                const int i = c0 + tl - l1;                           // source of lag l1 + 1 at target c0 + 1 + tl
+                if (i >= 0 && l1 < L) {
+                    const double *src = P.G + (((size_t)i * 6 + (i == 0 ? 5 : row)) * L + l1) * LT_ROW;
+#pragma unroll
+                    for (int cc = 0; cc < COLS; cc++) pre[k][cc] = src[cc];
+                }
+            }
+        }
+    }
+    // what fetch left in registers, to Gs ([<= CH][LC][ROWS][COLS]; the log-marginals behind it)
+    static __device__ __forceinline__ void store(const cw_params &P, int tid, int nc, double *Gs, const double (&pre)[NV][COLS], const double (&prelm)[NLM])
+    {
+        double *Lms = Gs + (size_t)CH * LC * ENT;
+        const int total = nc * LC * ROWS;
+#pragma unroll
+        for (int k = 0; k < NV; k++) {
+            const int u = tid + k * NTHR;
+            if (u < total) {
+#pragma unroll
+                for (int cc = 0; cc < COLS; cc++) Gs[(size_t)u * COLS + cc] = pre[k][cc];
+            }
+        }
+        if (P.mt) {
+#pragma unroll
+            for (int k = 0; k < NLM; k++) {
+                const int e = tid + k * NTHR;
+                if (e < nc * LT_ROW) Lms[e] = prelm[k];
+            }
+            __syncthreads();
+            // lag 1 of target tl, row r, column bb:  (0.0 + lm) + x1 -- the reference's first addition
+            for (int e = tid; e < nc * ENT; e += NTHR) {
+                const int tl = e / ENT, rc = e - tl * ENT, bb = rc % COLS;
+                double *gp = Gs + (size_t)tl * LC * ENT + rc;
+                *gp = Lms[tl * LT_ROW + bb] + *gp;
+            }
+        }
+    }
+};
+
+// The arg-max of a step over the candidates of a lane group (lane b of LPE holds acc of candidate b; shift = the group's first
+// bit in the wave's ballot): the pick, first wins (gretel.py:166-174).
+template <int R>
+__device__ __forceinline__ unsigned cw_pick(double acc, int b, unsigned shift)
+{
+    constexpr int LPE = cw_lanes(R);
+    if (R == 5 && b >= R) acc = -INFINITY;                   // (the idle lanes of the group)
+    double m = vmax_f64(acc, dpp_f64<0xB1>(acc));            // quad_perm [1,0,3,2]
+    m = vmax_f64(m, dpp_f64<0x4E>(m));                       // quad_perm [2,3,0,1]
+    if (R == 5) m = vmax_f64(m, dpp_f64<0x141>(m));          // row_half_mirror: the other quad of the eight lanes
+    // (R = 5: a NaN weight in first place is the reference's incumbent and stays it -- kernels.hpp, argmax8)
+    const unsigned long long win = __builtin_amdgcn_ballot_w64(R == 5 ? (acc == m || (b == 0 && acc != acc)) : acc == m);
+    return (unsigned)__builtin_ctz((unsigned)(win >> shift) & ((1u << LPE) - 1u));
+}
+
+// Pick d of position gt inside a segment of `len` positions into the word of picks; a full word (and the segment's last) goes to
+// hdst (stride CW_K: the entry's own words, or a pending slot's) where `write` says so.
+template <int R>
+__device__ __forceinline__ void cw_put_pick(unsigned d, int gt, int len, bool write, uint32_t *hdst, unsigned &word, int &word_i)
+{
+    constexpr int PPW = R == 4 ? 16 : 8, WB = R == 4 ? 2 : 4;     // picks per word of hist, bits each
+    word |= d << (WB * (gt % PPW));
+    if ((gt % PPW) == PPW - 1 || gt == len - 1) {
+        if (write) hdst[(size_t)word_i * CW_K] = word;
+        word = 0;
+        word_i++;
+    }
+}
+
+// The keys of the pool behind the segment being walked, for the closure search at its end: fetched while the walk has not begun
+// (one lane per key) instead of one dependent global load per key behind it.
+__device__ __forceinline__ void cw_stage_next(const cw_params &P, const cw_geom &g, int seg, int tid, cw_key *s_next, int *s_nn)
+{
+    if (tid < CW_K) s_next[tid] = seg + 1 < g.S ? P.keys[(size_t)(seg + 1) * CW_K + tid] : 0ull;
+    if (tid == 0) *s_nn = seg + 1 < g.S ? P.npool[seg + 1] : 0;      // (entries behind the count are leftovers of earlier tensors)
+}
+
+// -------------------------------------------------------------------------------------------------------------
 // k_cwalk: quad q of workgroup s walks pool entry q of segment s (if it has not been walked under this tensor), then
 // looks its exit state up in the next segment's pool.
 // -------------------------------------------------------------------------------------------------------------
 template <int LC, int R>
 __global__ void __launch_bounds__(CW_K * cw_lanes(R)) k_cwalk(cw_params P)
 {
-    constexpr int LPE = cw_lanes(R), BITS = cw_bits(R), NTHR = CW_K * LPE;
+    constexpr int LPE = cw_lanes(R), BITS = cw_bits(R);
     constexpr unsigned DMASK = (1u << BITS) - 1u;
-    constexpr int PPW = R == 4 ? 16 : 8, WB = R == 4 ? 2 : 4;     // picks per word of hist, bits each
     extern __shared__ __align__(16) unsigned char cw_smem[];
-    dev_state *st = P.st;
-    const dev_ctl c = load_ctl(st);
-    if (c.stop || c.lt_stale || c.cw_unres) return;
-    if (P.round > 0 && c.cw_open_at < 0) return;            // the chain closed in an earlier round
-    if (P.check_masks == 2 || (P.check_masks && c.cm_same == 0)) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) st->lt_stale = 1;
-        return;
-    }
-    if ((c.ranked != 0) != (R == 4)) {                      // the table is not in this instantiation's layout (it was rebuilt): the host looks again
-        if (blockIdx.x == 0 && threadIdx.x == 0) st->cw_unres = 2;
-        return;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        st->cur_hole = c.first_hole;      // (the flags stand until k_cemit re-arms them)
-        if (P.round == 0) st->cw_open_at = 0;           // a new path: its chain is open until a k_cscan says otherwise (round 0's may be skipped)
-    }
+    if (!cw_enter<R>(P)) return;
     const cw_geom g = cw_geometry(P.N, P.L);
     const int s = blockIdx.x, tid = threadIdx.x;
     if (s >= g.S) return;
@@ -218,14 +363,8 @@ __global__ void __launch_bounds__(CW_K * cw_lanes(R)) k_cwalk(cw_params P)
             if (dup) continue;
             int slot = n0;
             if (n0 >= CW_K) {
-                int mine = (tid == 0 && s == 0) ? 0x7fffffff : lh[tid], who = tid;
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) {
-                    const int om = __shfl_xor(mine, o), ow = __shfl_xor(who, o);
-                    if (om < mine || (om == mine && ow < who)) { mine = om; who = ow; }
-                }
-                if (mine >= P.stamp) continue;              // every entry was on a chain of this path (cannot happen: one per path)
-                slot = who;
+                slot = cw_evict(P, lh, s, tid);
+                if (slot < 0) continue;
             } else n0++;
             // (a request that arrives with its walk -- run-on -- joins as a walked entry: exit state and picks are copied)
             const bool ready = P.pend_ready_c && P.pend_ready_c[(size_t)s * CW_K + k] == P.stamp && P.stamp != 0;
@@ -262,80 +401,16 @@ __global__ void __launch_bounds__(CW_K * cw_lanes(R)) k_cwalk(cw_params P)
     bool active = live;                                     // this lane group still walks
     int pslot = 0;                                          // run-on: the pending slot of pool `seg` this walk belongs to
     uint32_t *hdst = P.hist + (size_t)s * nw_e * CW_K + q;  // where its words of picks go (stride CW_K): the entry's own, or a pending slot's
-    // The slice of a chunk: for target t = c0 + 1 + tl and lag l the rows of source t - l at that lag -- a run of COLS doubles
-    // per (tl, l, row) in G ([i][row][lag][col]), copied as a unit.  Position 0 carries '_' whatever the digit says (row 5),
-    // positions in front of it add +0.0.  The loads of chunk k+1 are issued before chunk k is walked and stay in registers
-    // under the walk: their latency is off the critical path.
-    constexpr int UNITS = CH * LC * ROWS;
-    constexpr int NV = (UNITS + NTHR - 1) / NTHR;
-    double pre[NV][COLS];
-    // marginal term: the log-marginals of the chunk's targets (column b: rank or symbol, like G's columns), fetched with the
-    // slice, added in front of the lag-1 entries once the slice stands in LDS
-    constexpr int NLM = (CH * LT_ROW + NTHR - 1) / NTHR;
-    double *Lms = Gs + (size_t)CH * LC * ENT;
-    double prelm[NLM];
-    auto fetch = [&](int c0) {
-        const int nc = t1 - c0 < CH ? t1 - c0 : CH;
-        if (P.mt) {
-#pragma unroll
-            for (int k = 0; k < NLM; k++) {
-                const int e = tid + k * NTHR;
-                const int tl = e / LT_ROW, bb = e - tl * LT_ROW;
-                const int tgt = c0 + 1 + tl;
-                prelm[k] = 0.0;
-                if (tl < nc && bb < R) prelm[k] = R == 4 ? P.rinfo[(size_t)tgt * RINFO + bb] : P.minfo[(size_t)tgt * MINFO + bb];
-            }
-        }
-        const int total = nc * LC * ROWS;
-#pragma unroll
-        for (int k = 0; k < NV; k++) {
-            const int u = tid + k * NTHR;
-#pragma unroll
-            for (int cc = 0; cc < COLS; cc++) pre[k][cc] = 0.0;
-            if (u < total) {
-                const int row = u % ROWS, l1 = (u / ROWS) % LC, tl = u / (ROWS * LC);
-                const int i = c0 + tl - l1;                           // source of lag l1 + 1 at target c0 + 1 + tl
-                if (i >= 0) {
-                    const double *src = P.G + (((size_t)i * 6 + (i == 0 ? 5 : row)) * LC + l1) * LT_ROW;
-#pragma unroll
-                    for (int cc = 0; cc < COLS; cc++) pre[k][cc] = src[cc];
-                }
-            }
-        }
-    };
-    auto store = [&](int c0) {
-        const int nc = t1 - c0 < CH ? t1 - c0 : CH;
-        const int total = nc * LC * ROWS;
-#pragma unroll
-        for (int k = 0; k < NV; k++) {
-            const int u = tid + k * NTHR;
-            if (u < total) {
-#pragma unroll
-                for (int cc = 0; cc < COLS; cc++) Gs[(size_t)u * COLS + cc] = pre[k][cc];
-            }
-        }
-        if (P.mt) {
-#pragma unroll
-            for (int k = 0; k < NLM; k++) {
-                const int e = tid + k * NTHR;
-                if (e < nc * LT_ROW) Lms[e] = prelm[k];
-            }
-            __syncthreads();
-            // lag 1 of target tl, row r, column bb:  (0.0 + lm) + x1 -- the reference's first addition
-            for (int e = tid; e < nc * ENT; e += NTHR) {
-                const int tl = e / ENT, rc = e - tl * ENT, bb = rc % COLS;
-                double *g = Gs + (size_t)tl * LC * ENT + rc;
-                *g = Lms[tl * LT_ROW + bb] + *g;
-            }
-        }
-    };
-    // the keys of the pool behind the segment being walked, for the closure search at its end: fetched while the walk has not
-    // begun (one lane per key) instead of one dependent global load per key behind it
+    // the next chunk's slice and its log-marginals, in registers under the walk (cw_slice)
+    typedef cw_slice<R, LC, CH> slice;
+    double pre[slice::NV][COLS];
+    double prelm[slice::NLM];
+    auto fetch = [&](int c0) { slice::fetch(P, LC, tid, c0, t1 - c0 < CH ? t1 - c0 : CH, pre, prelm); };
+    auto store = [&](int c0) { slice::store(P, tid, t1 - c0 < CH ? t1 - c0 : CH, Gs, pre, prelm); };
     __shared__ cw_key s_next[CW_K];
     __shared__ int s_nn;
     for (int hop = 0; ; hop++) {
-    if (tid < CW_K) s_next[tid] = seg + 1 < g.S ? P.keys[(size_t)(seg + 1) * CW_K + tid] : 0ull;
-    if (tid == 0) s_nn = seg + 1 < g.S ? P.npool[seg + 1] : 0;      // (entries behind the count are leftovers of earlier tensors)
+    cw_stage_next(P, g, seg, tid, s_next, &s_nn);
     fetch(t0);
     // the row addresses of the last LC picks in front of the segment: slot (LC - l) % LC = the pick l positions back
     constexpr unsigned ROWD = COLS;                              // doubles per row of a (target, lag) block
@@ -368,22 +443,10 @@ __global__ void __launch_bounds__(CW_K * cw_lanes(R)) k_cwalk(cw_params P)
                 double acc = x[0];
 #pragma unroll
                 for (int l = 2; l <= LC; l++) acc = acc + x[l - 1];
-                if (R == 5 && b >= R) acc = -INFINITY;                   // (the idle lanes of the group)
-                double m = vmax_f64(acc, dpp_f64<0xB1>(acc));            // quad_perm [1,0,3,2]
-                m = vmax_f64(m, dpp_f64<0x4E>(m));                       // quad_perm [2,3,0,1]
-                if (R == 5) m = vmax_f64(m, dpp_f64<0x141>(m));          // row_half_mirror: the other quad of the eight lanes
-                // (R = 5: a NaN weight in first place is the reference's incumbent and stays it -- kernels.hpp, argmax8)
-                const unsigned long long win = __builtin_amdgcn_ballot_w64(R == 5 ? (acc == m || (b == 0 && acc != acc)) : acc == m);
-                const unsigned d = (unsigned)__builtin_ctz((unsigned)(win >> shift) & ((1u << LPE) - 1u));       // first wins (gretel.py:166-174)
+                const unsigned d = cw_pick<R>(acc, b, shift);
                 sigma = (sigma << BITS) | (cw_key)d;                     // (what is shifted beyond LC picks is masked off behind the segment)
                 dig[u] = lane_base + d * (ROWD * 8u);
-                const int gt = c0 - t0 + v;                              // position inside the segment
-                word |= d << (WB * (gt % PPW));
-                if ((gt % PPW) == PPW - 1 || gt == t1 - t0 - 1) {
-                    if (active && b == 0) hdst[(size_t)word_i * CW_K] = word;
-                    word = 0;
-                    word_i++;
-                }
+                cw_put_pick<R>(d, c0 - t0 + v, t1 - t0, active && b == 0, hdst, word, word_i);
             }
         }, std::make_integer_sequence<int, CH>{});
     }
@@ -456,33 +519,17 @@ template <int R>
 __global__ void __launch_bounds__(CW_K * cw_lanes(R)) k_cwalkg(cw_params P)
 {
     constexpr int LPE = cw_lanes(R);
-    constexpr int PPW = R == 4 ? 16 : 8, WB = R == 4 ? 2 : 4;
     // ring[q][(t - l) & 127] = pick of position t - l, kept TWICE (slot + 128 as well): the eight picks a group of lags needs
     // then lie behind one another wherever the ring wraps, and their reads differ by a compile-time offset only
     __shared__ __align__(16) uint8_t ring[CW_K][2 * CW_MAX_LG];
     extern __shared__ __align__(16) unsigned char cwg_smem[];
     constexpr int ROWS = cw_rows(R), COLS = cw_cols(R), ENT = ROWS * COLS, NTHR = CW_K * LPE;
-    dev_state *st = P.st;
-    const dev_ctl c = load_ctl(st);
-    if (c.stop || c.lt_stale || c.cw_unres) return;
-    if (P.round > 0 && c.cw_open_at < 0) return;
-    if (P.check_masks == 2 || (P.check_masks && c.cm_same == 0)) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) st->lt_stale = 1;
-        return;
-    }
-    if ((c.ranked != 0) != (R == 4)) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) st->cw_unres = 2;
-        return;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        st->cur_hole = c.first_hole;
-        if (P.round == 0) st->cw_open_at = 0;               // a new path: its chain is open until a k_cscan says otherwise (round 0's may be skipped)
-    }
+    if (!cw_enter<R>(P)) return;
     const cw_geom g = cw_geometry(P.N, P.L);
     const int s = blockIdx.x, tid = threadIdx.x, L = P.L, LD = P.LD;
     if (s >= g.S) return;
-    // (1) pending states join the pool (as k_cwalk; equal hashes are confirmed on the bytes).  A request that arrives with its walk
-    // (run-on, round 4: as in k_cwalk) joins as a walked entry: exit state, its bytes and the picks are copied.
+    // (1) pending states join the pool, a full pool giving up an entry (cw_evict); equal hashes are confirmed on the bytes.  A request
+    // that arrives with its walk (run-on) joins as a walked entry: exit state, its bytes and the picks are copied.
     __shared__ int s_n;
     if (tid < 64) {
         int n0 = P.npool[s];
@@ -497,14 +544,8 @@ __global__ void __launch_bounds__(CW_K * cw_lanes(R)) k_cwalkg(cw_params P)
             if (__builtin_amdgcn_ballot_w64(mine_dup) != 0) continue;
             int slot = n0;
             if (n0 >= CW_K) {
-                int mine = (tid == 0 && s == 0) ? 0x7fffffff : lh[tid], who = tid;
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) {
-                    const int om = __shfl_xor(mine, o), ow = __shfl_xor(who, o);
-                    if (om < mine || (om == mine && ow < who)) { mine = om; who = ow; }
-                }
-                if (mine >= P.stamp) continue;
-                slot = who;
+                slot = cw_evict(P, lh, s, tid);
+                if (slot < 0) continue;
             } else n0++;
             const bool ready = P.pend_ready_c && P.pend_ready_c[(size_t)s * CW_K + k] == P.stamp && P.stamp != 0;
             if (tid == 0) {
@@ -644,20 +685,9 @@ __global__ void __launch_bounds__(CW_K * cw_lanes(R)) k_cwalkg(cw_params P)
                         if (l0 + u <= L) acc = acc + x[u];
                 }
             }
-            if (R == 5 && b >= R) acc = -INFINITY;
-            double m = vmax_f64(acc, dpp_f64<0xB1>(acc));
-            m = vmax_f64(m, dpp_f64<0x4E>(m));
-            if (R == 5) m = vmax_f64(m, dpp_f64<0x141>(m));
-            const unsigned long long win = __builtin_amdgcn_ballot_w64(R == 5 ? (acc == m || (b == 0 && acc != acc)) : acc == m);
-            const unsigned d = (unsigned)__builtin_ctz((unsigned)(win >> shift) & ((1u << LPE) - 1u));
+            const unsigned d = cw_pick<R>(acc, b, shift);
             if (active && b == 0) { ring[q][t & (CW_MAX_LG - 1)] = (uint8_t)d; ring[q][(t & (CW_MAX_LG - 1)) + CW_MAX_LG] = (uint8_t)d; }      // (read again at the earliest one step later, by this lane group only)
-            const int gt = t - t0 - 1;
-            word |= d << (WB * (gt % PPW));
-            if ((gt % PPW) == PPW - 1 || gt == t1 - t0 - 1) {
-                if (active && b == 0) hdst[(size_t)word_i * CW_K] = word;
-                word = 0;
-                word_i++;
-            }
+            cw_put_pick<R>(d, t - t0 - 1, t1 - t0, active && b == 0, hdst, word, word_i);
             __builtin_amdgcn_wave_barrier();
         }
     }
@@ -674,10 +704,7 @@ __global__ void __launch_bounds__(CW_K * cw_lanes(R)) k_cwalkg(cw_params P)
     }
     int go_on = 0;
     if (active && b == 0) {
-        unsigned long long hh = 0xcbf29ce484222325ull;      // (cw_hash_digits over the ring)
-        for (int l = 1; l <= L; l++) { hh ^= dg(l); hh *= 0x100000001b3ull; }
-        hh ^= hh >> 32; hh *= 0x9e3779b97f4a7c15ull; hh ^= hh >> 29;
-        const cw_key sigma = hh;
+        const cw_key sigma = cw_hash_digits(dg, L);
         if (hop == 0) {
             P.exits[(size_t)s * CW_K + q] = sigma;
             P.walked[(size_t)s * CW_K + q] = 1;
@@ -687,7 +714,8 @@ __global__ void __launch_bounds__(CW_K * cw_lanes(R)) k_cwalkg(cw_params P)
             __builtin_amdgcn_s_waitcnt(0);                  // (the exit state's bytes were stored by this lane group above)
             P.pend_ready[pe] = P.stamp;
         }
-        // closure, as in k_cwalk: an exit state the next pool does not hold asks to join it -- and, run-on, is walked on from here
+        // (3) closure: an exit state the next pool does not hold asks to join it -- and, run-on, is walked on from here (a missed
+        // match only costs a duplicate request, dropped at the merge)
         if (seg + 1 < g.S) {
             const cw_key *kn = P.keys + (size_t)(seg + 1) * CW_K;
             bool there = false;
@@ -746,34 +774,18 @@ __host__ __device__ constexpr int cw2_lc(int L, int R = 4) { return R == 4 ? (L 
 template <int LC, int R>
 __global__ void __launch_bounds__(CW_K * cw_lanes(R)) k_cwalk2(cw_params P)
 {
-    constexpr int LPE = cw_lanes(R), PPW = R == 4 ? 16 : 8, WB = R == 4 ? 2 : 4;
-    constexpr int ROWS = cw_rows(R), COLS = cw_cols(R), ENT = ROWS * COLS, NTHR = CW_K * LPE;
+    constexpr int LPE = cw_lanes(R), COLS = cw_cols(R), ENT = cw_rows(R) * COLS;
     constexpr int KP = cw2_parts(LC, R), CHA = cw2_chunk(LC, R);  // a block of LC steps: KP chunks of at most CHA targets
     static_assert(R == 4 ? (LC > CW_MAX_L && LC <= CW2_MAX_L) : (LC > CW_MAX_L5 && LC <= CW2_MAX_L5), "lag counts of k_cwalk2");
     static_assert(LC <= CW2_RING && (KP - 1) * CHA < LC, "a block's parts");
     __shared__ __align__(16) uint8_t ring[CW_K][CW2_RING];  // ring[q][t & 63] = pick at position t
     extern __shared__ __align__(16) unsigned char cw2_smem[];
-    dev_state *st = P.st;
-    const dev_ctl c = load_ctl(st);
-    if (c.stop || c.lt_stale || c.cw_unres) return;
-    if (P.round > 0 && c.cw_open_at < 0) return;
-    if (P.check_masks == 2 || (P.check_masks && c.cm_same == 0)) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) st->lt_stale = 1;
-        return;
-    }
-    if ((c.ranked != 0) != (R == 4)) {                      // the table is not in this instantiation's layout (it was rebuilt): the host looks again
-        if (blockIdx.x == 0 && threadIdx.x == 0) st->cw_unres = 2;
-        return;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        st->cur_hole = c.first_hole;
-        if (P.round == 0) st->cw_open_at = 0;
-    }
+    if (!cw_enter<R>(P)) return;
     const cw_geom g = cw_geometry(P.N, P.L);
     const int s = blockIdx.x, tid = threadIdx.x, L = P.L, LD = P.LD;
     if (s >= g.S) return;
-    // (1) pending states join the pool: k_cwalkg's merge, word for word (equal hashes are confirmed on the bytes; a request that
-    // arrives with its walk joins as a walked entry)
+    // (1) pending states join the pool, a full pool giving up an entry (cw_evict); equal hashes are confirmed on the bytes, and a
+    // request that arrives with its walk joins as a walked entry
     __shared__ int s_n;
     if (tid < 64) {
         int n0 = P.npool[s];
@@ -788,14 +800,8 @@ __global__ void __launch_bounds__(CW_K * cw_lanes(R)) k_cwalk2(cw_params P)
             if (__builtin_amdgcn_ballot_w64(mine_dup) != 0) continue;
             int slot = n0;
             if (n0 >= CW_K) {
-                int mine = (tid == 0 && s == 0) ? 0x7fffffff : lh[tid], who = tid;
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) {
-                    const int om = __shfl_xor(mine, o), ow = __shfl_xor(who, o);
-                    if (om < mine || (om == mine && ow < who)) { mine = om; who = ow; }
-                }
-                if (mine >= P.stamp) continue;
-                slot = who;
+                slot = cw_evict(P, lh, s, tid);
+                if (slot < 0) continue;
             } else n0++;
             const bool ready = P.pend_ready_c && P.pend_ready_c[(size_t)s * CW_K + k] == P.stamp && P.stamp != 0;
             if (tid == 0) {
@@ -830,70 +836,17 @@ __global__ void __launch_bounds__(CW_K * cw_lanes(R)) k_cwalk2(cw_params P)
             ring[q][(s * g.seglen + 1 - l) & (CW2_RING - 1)] = P.keys_d[((size_t)s * CW_K + q) * LD + (l - 1)];
     __syncthreads();
     double *Gs = reinterpret_cast<double *>(cw2_smem);      // [<= CHA][LC][ROWS][COLS]
-    double *Lms = Gs + (size_t)CHA * LC * ENT;
     bool active = live;
     int seg = s, pslot = 0;
     uint32_t *hdst = P.hist + (size_t)s * nw_e * CW_K + q;
-    // the slice of a chunk (k_cwalk's, with the lag count known at run time: blocks of lags beyond L are zeros), fetched into
-    // registers while the chunk before is walked
-    constexpr int UNITS = CHA * LC * ROWS;
-    constexpr int NV = (UNITS + NTHR - 1) / NTHR;
-    constexpr int NLM = (CHA * LT_ROW + NTHR - 1) / NTHR;
-    double pre[NV][COLS];
-    double prelm[NLM];
-    auto fetch = [&](int c0, int nc) {
-        if (P.mt) {
-#pragma unroll
-            for (int k = 0; k < NLM; k++) {
-                const int e = tid + k * NTHR;
-                const int tl = e / LT_ROW, bb = e - tl * LT_ROW;
-                prelm[k] = 0.0;
-                if (tl < nc && bb < R) prelm[k] = R == 4 ? P.rinfo[(size_t)(c0 + 1 + tl) * RINFO + bb] : P.minfo[(size_t)(c0 + 1 + tl) * MINFO + bb];
-            }
-        }
-        const int total = nc * LC * ROWS;
-#pragma unroll
-        for (int k = 0; k < NV; k++) {
-            const int u = tid + k * NTHR;
-#pragma unroll
-            for (int cc = 0; cc < COLS; cc++) pre[k][cc] = 0.0;
-            if (u < total) {
-                const int row = u % ROWS, l1 = (u / ROWS) % LC, tl = u / (ROWS * LC);
-                const int i = c0 + tl - l1;                           // source of lag l1 + 1 at target c0 + 1 + tl
-                if (i >= 0 && l1 < L) {
-                    const double *src = P.G + (((size_t)i * 6 + (i == 0 ? 5 : row)) * L + l1) * LT_ROW;
-#pragma unroll
-                    for (int cc = 0; cc < COLS; cc++) pre[k][cc] = src[cc];
-                }
-            }
-        }
-    };
-    auto store = [&](int nc) {
-        const int total = nc * LC * ROWS;
-#pragma unroll
-        for (int k = 0; k < NV; k++) {
-            const int u = tid + k * NTHR;
-            if (u < total) {
-#pragma unroll
-                for (int cc = 0; cc < COLS; cc++) Gs[(size_t)u * COLS + cc] = pre[k][cc];
-            }
-        }
-        if (P.mt) {
-#pragma unroll
-            for (int k = 0; k < NLM; k++) {
-                const int e = tid + k * NTHR;
-                if (e < nc * LT_ROW) Lms[e] = prelm[k];
-            }
-            __syncthreads();
-            for (int e = tid; e < nc * ENT; e += NTHR) {              // lag 1: (0.0 + lm) + x1, the reference's first addition
-                const int tl = e / ENT, rc = e - tl * ENT, bb = rc % COLS;
-                double *gp = Gs + (size_t)tl * LC * ENT + rc;
-                *gp = Lms[tl * LT_ROW + bb] + *gp;
-            }
-        }
-    };
-    // the hashes of the pool behind the segment being walked, for the closure search at its end (as k_cwalk: one lane per key while
-    // the walk has not begun, instead of a chain of dependent global loads behind it)
+    // the slice of a chunk (cw_slice, the lag count known at run time: blocks of lags beyond L are zeros), fetched into registers
+    // while the chunk before is walked
+    typedef cw_slice<R, LC, CHA> slice;
+    double pre[slice::NV][COLS];
+    double prelm[slice::NLM];
+    auto fetch = [&](int c0, int nc) { slice::fetch(P, L, tid, c0, nc, pre, prelm); };
+    auto store = [&](int nc) { slice::store(P, tid, nc, Gs, pre, prelm); };
+    // the hashes of the pool behind the segment being walked, for the closure search at its end (cw_stage_next)
     __shared__ cw_key s_next[CW_K];
     __shared__ int s_nn;
     constexpr int NW4 = (LC + 3) / 4;                       // words of a state
@@ -902,8 +855,7 @@ __global__ void __launch_bounds__(CW_K * cw_lanes(R)) k_cwalk2(cw_params P)
     for (int hop = 0; ; hop++) {
     const int t0 = seg * g.seglen;
     const int t1 = t0 + g.seglen < P.N ? t0 + g.seglen : P.N;
-    if (tid < CW_K) s_next[tid] = seg + 1 < g.S ? P.keys[(size_t)(seg + 1) * CW_K + tid] : 0ull;
-    if (tid == 0) s_nn = seg + 1 < g.S ? P.npool[seg + 1] : 0;      // (entries behind the count are leftovers of earlier tensors)
+    cw_stage_next(P, g, seg, tid, s_next, &s_nn);
     int word_i = 0;
     unsigned word = 0;
     constexpr unsigned ROWD = COLS;
@@ -920,22 +872,10 @@ __global__ void __launch_bounds__(CW_K * cw_lanes(R)) k_cwalk2(cw_params P)
         double acc = x[0];
 #pragma unroll
         for (int l = 2; l <= LC; l++) acc = acc + x[l - 1];
-        if (R == 5 && b >= R) acc = -INFINITY;                   // (the idle lanes of the group)
-        double m = vmax_f64(acc, dpp_f64<0xB1>(acc));            // quad_perm [1,0,3,2]
-        m = vmax_f64(m, dpp_f64<0x4E>(m));                       // quad_perm [2,3,0,1]
-        if (R == 5) m = vmax_f64(m, dpp_f64<0x141>(m));          // row_half_mirror: the other quad of the eight lanes
-        // (R = 5: a NaN weight in first place is the reference's incumbent and stays it -- kernels.hpp, argmax8)
-        const unsigned long long win = __builtin_amdgcn_ballot_w64(R == 5 ? (acc == m || (b == 0 && acc != acc)) : acc == m);
-        const unsigned d = (unsigned)__builtin_ctz((unsigned)(win >> shift) & ((1u << LPE) - 1u));       // first wins (gretel.py:166-174)
+        const unsigned d = cw_pick<R>(acc, b, shift);
         const int t = c0 + 1 + tl;
         if (active && b == 0) ring[q][t & (CW2_RING - 1)] = (uint8_t)d;      // (read again behind the segment only)
-        const int gt = t - t0 - 1;
-        word |= d << (WB * (gt % PPW));
-        if ((gt % PPW) == PPW - 1 || gt == t1 - t0 - 1) {
-            if (active && b == 0) hdst[(size_t)word_i * CW_K] = word;
-            word = 0;
-            word_i++;
-        }
+        cw_put_pick<R>(d, t - t0 - 1, t1 - t0, active && b == 0, hdst, word, word_i);
         return d;
     };
     int c0 = t0;
@@ -968,7 +908,7 @@ __global__ void __launch_bounds__(CW_K * cw_lanes(R)) k_cwalk2(cw_params P)
     // `pslot` of pool `seg`.  Every lane of the group holds the whole state: each then compares its share of the next pool.
     __syncthreads();
     uint32_t xw[NW4];
-    unsigned long long hh = 0xcbf29ce484222325ull;          // (cw_hash_digits)
+    cw_key hh = CW_HASH_SEED;
 #pragma unroll
     for (int j = 0; j < NW4; j++) {
         uint32_t w = 0;
@@ -977,12 +917,11 @@ __global__ void __launch_bounds__(CW_K * cw_lanes(R)) k_cwalk2(cw_params P)
             const int l = 4 * j + e + 1, i = t1 + 1 - l;
             const uint32_t d = (l <= L && i >= 1) ? (uint32_t)ring[q][i & (CW2_RING - 1)] : 0u;
             w |= d << (8 * e);
-            if (l <= L) { hh ^= (unsigned long long)d; hh *= 0x100000001b3ull; }
+            if (l <= L) hh = cw_hash_step(hh, d);
         }
         xw[j] = w;
     }
-    hh ^= hh >> 32; hh *= 0x9e3779b97f4a7c15ull; hh ^= hh >> 29;
-    const cw_key sigma = hh;
+    const cw_key sigma = cw_hash_finish(hh);
     if (active) {
         uint32_t *xd = reinterpret_cast<uint32_t *>(hop == 0 ? P.exits_d + ((size_t)s * CW_K + q) * LD : P.pend_exit_d + ((size_t)seg * CW_K + pslot) * LD);
 #pragma unroll
@@ -1015,7 +954,8 @@ __global__ void __launch_bounds__(CW_K * cw_lanes(R)) k_cwalk2(cw_params P)
             P.pend_exit[pe] = sigma;
             P.pend_ready[pe] = P.stamp;                     // (read by the owner in a later launch: the bytes above are there by then)
         }
-        // closure, as in k_cwalk: an exit state the next pool does not hold asks to join it -- and, run-on, is walked on from here
+        // (3) closure: an exit state the next pool does not hold asks to join it -- and, run-on, is walked on from here (a missed
+        // match only costs a duplicate request, dropped at the merge)
         if (seg + 1 < g.S && !there) {
             const int slot = atomicAdd(&P.npend[seg + 1], 1);
             if (slot < CW_K) {

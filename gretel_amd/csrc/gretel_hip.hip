@@ -1654,6 +1654,26 @@ static int alloc_cw(gh_handle *h)
     return GH_OK;
 }
 
+// the request lists of a launch: the set it appends to (h->cw_pp picks it) and the set it consumes, which the launch before
+// appended to (cwalk.hpp); the lists of run-on results only where P.runon says walkers run on
+static void cw_pend_sets(const gh_handle *h, const cw_geom &g, cw_params &P)
+{
+    const size_t nw = (size_t)(h->cw_wide ? g.NW5 : g.NW);
+    const size_t a = (size_t)(h->cw_pp & 1), c = a ^ 1;
+    P.pend = h->cw_pend + a * h->cw_S * CW_K;            P.pend_c = h->cw_pend + c * h->cw_S * CW_K;
+    P.npend = h->cw_npend + a * h->cw_S;                 P.npend_c = h->cw_npend + c * h->cw_S;
+    if (P.runon > 0) {
+        P.pend_exit = h->cw_pend_exit + a * h->cw_S * CW_K;   P.pend_exit_c = h->cw_pend_exit + c * h->cw_S * CW_K;
+        P.pend_ready = h->cw_pend_ready + a * h->cw_S * CW_K; P.pend_ready_c = h->cw_pend_ready + c * h->cw_S * CW_K;
+        P.phist = h->cw_phist + a * g.S * nw * CW_K;          P.phist_c = h->cw_phist + c * g.S * nw * CW_K;
+    }
+    if (cw_digit_mode(h)) {
+        const size_t bytes = (size_t)g.S * CW_K * h->cw_LD;
+        P.pend_d = h->cw_pend_d + a * bytes;             P.pend_d_c = h->cw_pend_d + c * bytes;
+        P.pend_exit_d = h->cw_pend_exit_d + a * bytes;   P.pend_exit_d_c = h->cw_pend_exit_d + c * bytes;
+    }
+}
+
 static cw_params cw_make_params(gh_handle *h, uint8_t *d_path, double *d_lmsel)
 {
     cw_params P;
@@ -1673,33 +1693,11 @@ static cw_params cw_make_params(gh_handle *h, uint8_t *d_path, double *d_lmsel)
     if (cw_digit_mode(h) && !cw2_ok(h)) runon = 0;
     runon = env_int("GH_CW_RUNON", runon);
     if (runon > CW_RUNON) runon = CW_RUNON;
-    const bool no_runon = runon <= 0;
     P.runon = runon;
-    P.pend_c = P.pend; P.npend_c = P.npend;
-    {
-        // the set this launch appends to / the set it consumes (what the launch before appended to)
-        const cw_geom gg = cw_geometry(h->N, h->L);
-        const size_t nw = (size_t)(h->cw_wide ? gg.NW5 : gg.NW);
-        const size_t a = (size_t)(h->cw_pp & 1), c = a ^ 1;
-        P.pend = h->cw_pend + a * h->cw_S * CW_K;            P.pend_c = h->cw_pend + c * h->cw_S * CW_K;
-        P.npend = h->cw_npend + a * h->cw_S;                 P.npend_c = h->cw_npend + c * h->cw_S;
-        if (!no_runon) {
-            P.pend_exit = h->cw_pend_exit + a * h->cw_S * CW_K;   P.pend_exit_c = h->cw_pend_exit + c * h->cw_S * CW_K;
-            P.pend_ready = h->cw_pend_ready + a * h->cw_S * CW_K; P.pend_ready_c = h->cw_pend_ready + c * h->cw_S * CW_K;
-            P.phist = h->cw_phist + a * gg.S * nw * CW_K;         P.phist_c = h->cw_phist + c * gg.S * nw * CW_K;
-        }
-        if (cw_digit_mode(h)) {
-            const size_t bytes = (size_t)gg.S * CW_K * h->cw_LD;
-            P.pend_d = h->cw_pend_d + a * bytes;             P.pend_d_c = h->cw_pend_d + c * bytes;
-            P.pend_exit_d = h->cw_pend_exit_d + a * bytes;   P.pend_exit_d_c = h->cw_pend_exit_d + c * bytes;
-        }
-    }
+    cw_pend_sets(h, ggr, P);
     if (cw_digit_mode(h)) {
         P.keys_d = h->cw_keys_d; P.exits_d = h->cw_exits_d; P.LD = h->cw_LD;
-        unsigned long long hh = 0xcbf29ce484222325ull;      // cw_hash_digits of L zero bytes: the start state
-        for (int l = 0; l < h->L; l++) { hh ^= 0u; hh *= 0x100000001b3ull; }
-        hh ^= hh >> 32; hh *= 0x9e3779b97f4a7c15ull; hh ^= hh >> 29;
-        P.key0 = hh;
+        P.key0 = cw_hash_digits([](int) { return 0u; }, h->L);      // the start state: L zero bytes
     }
     return P;
 }
@@ -1718,6 +1716,14 @@ static void launch_cwalk2_lc(const cw_params &P, hipStream_t stream, int S, int 
     hipLaunchKernelGGL((k_cwalk2<LC, R>), dim3(S), dim3(CW_K * cw_lanes(R)), cw2_lds_bytes(LC, R), stream, P);
 }
 
+template <int R>
+static void launch_cwalkg(const cw_params &P, hipStream_t stream, int S, int dev)
+{
+    const size_t lds = cwg_lds_bytes(P.L, R);
+    lds_limit<k_cwalkg<R>>(lds, dev);
+    hipLaunchKernelGGL((k_cwalkg<R>), dim3(S), dim3(CW_K * cw_lanes(R)), lds, stream, P);
+}
+
 // the kernels of one path: `rounds` x (walk what is new, link + chain), emit
 static int launch_cw_path(gh_handle *h, uint8_t *d_path, double *d_lmsel, int rounds, int check_masks, bool resume = false)
 {
@@ -1731,14 +1737,9 @@ static int launch_cw_path(gh_handle *h, uint8_t *d_path, double *d_lmsel, int ro
         P.round = resume ? r + 1 : r;                       // (a resumed path continues behind the rounds already run)
         P.check_masks = (r == 0 && !resume) ? check_masks : 0;
         P.last_round = r == rounds - 1;
-        {
-            // every k_cwalk launch appends to the request lists the launch before consumed, and the other way round
-            h->cw_pp++;
-            const cw_params Q = cw_make_params(h, d_path, d_lmsel);
-            P.pend = Q.pend; P.npend = Q.npend; P.pend_exit = Q.pend_exit; P.pend_ready = Q.pend_ready; P.phist = Q.phist;
-            P.pend_c = Q.pend_c; P.npend_c = Q.npend_c; P.pend_exit_c = Q.pend_exit_c; P.pend_ready_c = Q.pend_ready_c; P.phist_c = Q.phist_c;
-            P.pend_d = Q.pend_d; P.pend_d_c = Q.pend_d_c; P.pend_exit_d = Q.pend_exit_d; P.pend_exit_d_c = Q.pend_exit_d_c;
-        }
+        // every k_cwalk launch appends to the request lists the launch before consumed, and the other way round
+        h->cw_pp++;
+        cw_pend_sets(h, g, P);
         if (r == 0) prof_begin(h, GH_K_SEG);                // (bench.py: the pool walker alone, first round of a path)
         if (cw_digit_mode(h) && cw2_ok(h) && h->cw_wide) {
             switch (cw2_lc(h->L, 5)) {
@@ -1760,9 +1761,8 @@ static int launch_cw_path(gh_handle *h, uint8_t *d_path, double *d_lmsel, int ro
                 default: launch_cwalk2_lc<64>(P, h->stream, g.S, h->dev); break;
             }
         } else if (cw_digit_mode(h)) {
-            const size_t lds_g = cwg_lds_bytes(h->L, h->cw_wide ? 5 : 4);
-            if (!h->cw_wide) { lds_limit<k_cwalkg<4>>(lds_g, h->dev); hipLaunchKernelGGL((k_cwalkg<4>), dim3(g.S), dim3(CW_K * cw_lanes(4)), lds_g, h->stream, P); }
-            else { lds_limit<k_cwalkg<5>>(lds_g, h->dev); hipLaunchKernelGGL((k_cwalkg<5>), dim3(g.S), dim3(CW_K * cw_lanes(5)), lds_g, h->stream, P); }
+            if (!h->cw_wide) launch_cwalkg<4>(P, h->stream, g.S, h->dev);
+            else launch_cwalkg<5>(P, h->stream, g.S, h->dev);
         } else
         switch (h->L) {
             // (the table over the symbols: 3 bits per pick, CW_MAX_L5 lags in a state)
