@@ -16,6 +16,7 @@ GH_OK = 0
 GH_ERR_ARG, GH_ERR_HIP, GH_ERR_BAND, GH_ERR_SYMBOL, GH_ERR_NOMEM, GH_ERR_STATE = -1, -2, -3, -4, -5, -6
 GH_STORAGE = {"f32": 0, "f64": 1}
 GH_COND = {"A": 0, "B": 1, "C": 2, "D": 3, "E": 4}
+GH_BEAM_MAX = 32
 GH_K = {"fill": 0, "marg": 1, "lt": 2, "walk": 3, "reweight": 4, "seg": 5, "rwseg": 6}
 
 
@@ -133,6 +134,9 @@ def load():
         "gh_debug_pool_geometry": [i32, i32, i32, vp],
         "gh_assign_reads": [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, P(gh_assign_stats)],
         "gh_score_paths": [vp, vp, i32, vp, vp, vp, vp],
+        "gh_beam_paths": [vp, i32, vp, vp, P(i32), P(i32)],
+        "gh_beam_spin": [vp, i32, i32, dbl, vp, vp, vp, P(i32), P(i32)],
+        "gh_beam_info": [vp, vp],
         "gh_coverage_sites": [i32, vp, vp, vp, i64, C.c_int32, C.c_int32, C.c_int32, vp, vp],
     }
     for name, args in sigs.items():

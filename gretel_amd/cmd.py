@@ -12,6 +12,9 @@ and, with --assign-reads (no reference counterpart; INTEGRATION.md "Read assignm
     <out>/gretel.support  "# n_reads n_informative n_unique n_ambiguous n_unexplained" + one line per haplotype:
                           i_0, unique, shared, mismatches, unique / n_unique
 
+and, with --beam B (INTEGRATION.md "Beam search"), the same files from paths that are each the best of a beam of B hypotheses over
+the chain likelihood; --beam 1 writes what a run without the flag writes.
+
 and, with --score-paths / --known FASTA (INTEGRATION.md "Scoring haplotypes"), against the matrix as it was before any reweighting:
     <out>/gretel.scores   "# N L cond_mode marginal_term" + one line per recovered haplotype: i_0, ll_chain, hp_original, n_greedy,
                           n_on, first_off, min_margin, argmin_margin and the genomic position of argmin_margin
@@ -28,6 +31,7 @@ from . import util
 from .hansel import Hansel
 
 MIN_REMOVE = 0.01          # cmd.py:157
+BEAM_MAX = 32              # include/gretel_hip.h: GH_BEAM_MAX
 
 
 def build_parser():
@@ -54,6 +58,8 @@ def build_parser():
     p.add_argument("--pepper", action="store_true", help="permissive read filter (pysam stepper 'all' in the reference)")
     add_assign_options(p)
     add_score_options(p)
+    p.add_argument("--beam", type=int, default=0, metavar="B", help="recover every path as the best of a beam of B hypotheses over "
+                   "the chain likelihood instead of the greedy walk (1..%d; 1 = the greedy walk; 0 = off) [default: 0]" % BEAM_MAX)
     p.add_argument("--version", action="version", version="%(prog)s " + __version__)
     return p
 
@@ -160,10 +166,12 @@ def _add_path(paths, i, key, hansel_path, hp_current, hp_original, magnitude):
     rec["hp_original"].append(hp_original)
 
 
-def recover(hansel, n_snps, max_paths, log=None):
+def recover(hansel, n_snps, max_paths, log=None, beam=0):
     """cmd.py:148-179 on the device; returns the PATHS table in order of discovery.  The spins have already
-    happened when the notes are written, but the notes are the reference's, in the reference's order."""
-    return paths_of_spin(hansel, hansel.spin(max_paths, MIN_REMOVE), log)
+    happened when the notes are written, but the notes are the reference's, in the reference's order.
+    beam >= 1 (--beam): every path is the best of a beam of that many hypotheses (Hansel.beam_spin)."""
+    res = hansel.beam_spin(beam, max_paths, MIN_REMOVE) if beam else hansel.spin(max_paths, MIN_REMOVE)
+    return paths_of_spin(hansel, res, log)
 
 
 def paths_of_spin(hansel, res, log=None):
@@ -330,9 +338,29 @@ def check_assign_options(args):
     return None
 
 
+def debug_hpos_of(args):
+    """The SNP ranks of --debughpos (cmd.py:120-121: whatever does not parse as a number is dropped)."""
+    out = []
+    for x in (args.debughpos or "").split(","):
+        try:
+            out.append(int(x))
+        except ValueError:
+            pass
+    return out
+
+
+def check_beam_options(args):
+    """The refusals of --beam (before any BAM read or GPU call): a message, or None."""
+    if args.beam < 0 or args.beam > BEAM_MAX:
+        return "--beam must be 0 (off) or 1..%d" % BEAM_MAX
+    if args.beam and debug_hpos_of(args):
+        return "--beam cannot be combined with --debughpos, which prints the branch weights of the greedy walk"
+    return None
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    bad = check_assign_options(args) or check_score_options(args)
+    bad = check_assign_options(args) or check_score_options(args) or check_beam_options(args)
     if bad:
         sys.stderr.write("[FAIL] %s\n" % bad)
         return 2
@@ -366,16 +394,11 @@ def main(argv=None):
         sys.exit(1)                                                               # cmd.py:118
     if not args.quiet:
         print_snp_table(hansel, vcf_h)
-    debug_hpos = []
-    for x in (args.debughpos or "").split(","):
-        try:
-            debug_hpos.append(int(x))
-        except ValueError:
-            pass
+    debug_hpos = debug_hpos_of(args)
     if debug_hpos:
         paths = recover_with_debug(hansel, vcf_h["N"], args.paths, debug_hpos)
     else:
-        paths = recover(hansel, vcf_h["N"], args.paths)
+        paths = recover(hansel, vcf_h["N"], args.paths, beam=args.beam)
     write_outputs(paths, hansel, vcf_h, args)
     if args.assign_reads:
         write_support(paths, hansel, args)

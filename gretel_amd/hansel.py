@@ -352,6 +352,47 @@ class Hansel:
         out.update((k, recs[k].copy()) for k in SCORE_REC.names)
         return out
 
+    def beam_paths(self, width):
+        """Beam search of `width` (1..32) hypotheses over the chain likelihood on the tensor as it is now (gh_beam_paths; the
+        definition: INTEGRATION.md "Beam search").  Returns dict(n, hole_at, paths uint8[n][N+1] in rank order, ll_chain
+        float64[n]); at a hole n = 0 and `prefix` holds what the rank-0 hypothesis had walked.  The tensor is not touched."""
+        self._ensure()
+        width = int(width)
+        paths = np.zeros((max(1, min(width, _lib.GH_BEAM_MAX)), self.n + 1), dtype=np.uint8)
+        ll = np.zeros(len(paths))
+        n, hole = C.c_int(), C.c_int()
+        check(self._lib.gh_beam_paths(self._h, width, _p(paths), _p(ll), C.byref(n), C.byref(hole)))
+        out = dict(n=n.value, hole_at=hole.value, paths=paths[:n.value], ll_chain=ll[:n.value])
+        if hole.value:
+            out["prefix"] = paths[0, :hole.value].copy()
+        return out
+
+    def beam_spin(self, width, max_paths=100, min_remove=0.01):
+        """gretel/cmd.py:148-179 with the rank-0 path of a beam of `width` in place of generate_path (gh_beam_spin: a host loop,
+        not the throughput path).  Returns spin()'s dict plus ll_chain float64[n], the beam score of every path."""
+        self._ensure()
+        nrec = C.sizeof(_lib.gh_path_rec) // 8
+        paths = np.empty((max(0, max_paths), self.n + 1), dtype=np.uint8)
+        recs = np.empty((max(1, max_paths), nrec), dtype=np.float64)
+        ll = np.zeros(max(1, max_paths))
+        n, hole = C.c_int(), C.c_int()
+        check(self._lib.gh_beam_spin(self._h, int(width), int(max_paths), float(min_remove), _p(paths), _p(recs), _p(ll),
+                                     C.byref(n), C.byref(hole)))
+        k = n.value
+        if k:
+            self.is_weighted = True
+        r = recs[:k]
+        return dict(n=k, hole_at=hole.value, paths=paths[:k], hp_current=r[:, 0].copy(), hp_original=r[:, 1].copy(),
+                    ratio=r[:, 2].copy(), magnitude=r[:, 3].copy(), min_marginal=r[:, 4].copy(), ll_chain=ll[:k].copy())
+
+    def beam_info(self):
+        """The last beam run on this handle (gh_beam_info): (1 if the table slice was staged through LDS, source positions the
+        LDS ring holds, threads of the walk workgroup, bytes of the beam's device scratch)."""
+        self._ensure()
+        out = np.zeros(4, dtype=np.int64)
+        check(self._lib.gh_beam_info(self._h, _p(out)))
+        return tuple(int(v) for v in out)
+
     def clear(self):
         self._staged = []
         if self._h is not None:

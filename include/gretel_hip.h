@@ -272,6 +272,49 @@ typedef struct {
 int gh_score_paths(gh_t *h, const uint8_t *paths, int n_paths, gh_score_rec *recs,
                    double *weight, double *margin, uint8_t *pick);
 
+/* Beam search over the chain likelihood (no reference counterpart; INTEGRATION.md "Beam search").  gh_generate_path keeps, at
+ * each SNP, the one candidate of largest edge weight; a beam of width B, 1 <= B <= GH_BEAM_MAX, keeps the B best path prefixes by
+ * their summed weight -- the ll_chain of gh_score_paths -- over the same weights.  An opt-in search and a diagnostic (is there a
+ * path of higher chain likelihood that the greedy walk missed?), not a better default.  With the handle's L, conditional, marginal
+ * term and candidate order:
+ *   A hypothesis is a path prefix x[0..p], x[0] = '_', and a score.  At p = 0 there is one, of score +0.0.
+ *   Step p = 1..N: cm(p) is the candidate set of p (it does not depend on the history).  Empty: the search stops, hole_at = p
+ *   (below).  Otherwise every hypothesis of rank k = 0..n-1 spawns one child per c in cm(p), of weight w = w_p[c | x_k] -- what
+ *   gh_edge_weights_at(h, p, x_k, ...) returns for c bit for bit: the marginal term first, then lags 1, 2, ... in that order --
+ *   and score score_k + w, one binary64 addition.
+ *   The children are put in a total order by (1) score descending, (2) parent rank ascending, (3) w descending, (4) index of c in
+ *   cand_order ascending; comparisons are plain IEEE > and ==, so equal -inf scores tie.  The first min(B, #children) become
+ *   the hypotheses of ranks 0, 1, ... at step p.  (For one parent this is "the first of cand_order, replaced only by a
+ *   strictly larger weight": fl(s + .) is monotone, and equal sums fall back to w, then to the order.  Hence B = 1 is
+ *   gh_generate_path.)
+ *   Result: the n_out hypotheses alive at p = N in rank order: their paths [n_out][N + 1] (index 0 = 6, '_') and scores
+ *   ll_chain[n_out], each the sequential sum from 0.0 in ascending p, so equal to gh_score_paths(...).ll_chain of that path bit
+ *   for bit, with n_on == N.  Distinct hypotheses are distinct paths; hypotheses that share their last L symbols are NOT merged.
+ *   Hole: n_out = 0, hole_at = p, ll_chain is not written; row 0 of paths_out, indices [0..p-1], holds the prefix of the rank-0
+ *   hypothesis at step p - 1 (at B = 1 what gh_generate_path leaves).
+ * GH_ERR_ARG for a null h, paths_out, n_out or hole_at (gh_beam_spin: recs too), a width outside 1..GH_BEAM_MAX, max_paths < 0,
+ * min(L, N) > 2048 (the histories live in on-chip memory), or a handle created with offer_zero: a zero-count candidate can weigh
+ * NaN (-inf + +inf), which no order ranks.  GH_ERR_STATE before any fill, add or import.  GH_ERR_NOMEM when the scratch cannot be
+ * had: the beam builds its own conditional table in a block of the handle that GROWS WITH N * L -- N * (30 L + 6) * 8 bytes (12 MB
+ * at 10k SNPs and L = 5, 134 MB at 50k and L = 11), kept until gh_destroy.
+ * gh_beam_paths only reads the tensor: the band, L, the fill statistics, the snapshot, the handle's conditional tables and the
+ * results of a following gh_spin stay as they are, bit for bit.
+ * gh_beam_spin is the recovery loop of gretel/cmd.py:148-179 with the beam's rank-0 path in place of generate_path: per path, run
+ * the beam; hp_current, hp_original (under the snapshot, taken now if there is none) and min_marginal of that path as
+ * gh_score_paths gives them on the tensor at that moment; ratio = max(min_marginal, min_remove); magnitude = the removed mass of
+ * gh_reweight_path; it stops at the first hole, as gh_spin does.  ll_chain[s] = the beam score of path s.  A host loop over
+ * those pieces, one beam launch sequence and two host round trips per path: NOT the throughput path (that is gh_spin).  At
+ * width 1 its results are gh_spin's.
+ * gh_beam_info, the last beam run on the handle: out[0] = 1 if the table slice was staged through on-chip memory (LDS), 0 if it
+ * was read from global memory (L >= 19); out[1] = source positions the LDS ring holds (it is refilled one position per step;
+ * 0 if not staged); out[2] = threads of the walk workgroup; out[3] = bytes of the beam's device scratch. */
+#define GH_BEAM_MAX 32
+int gh_beam_paths(gh_t *h, int width, uint8_t *paths_out /*[width][N+1]*/, double *ll_chain /*[width], may be NULL*/,
+                  int *n_out, int *hole_at);
+int gh_beam_spin(gh_t *h, int width, int max_paths, double min_remove, uint8_t *paths_out /*[max_paths][N+1]*/,
+                 gh_path_rec *recs, double *ll_chain /*[max_paths], may be NULL*/, int *n_out, int *hole_at);
+int gh_beam_info(const gh_t *h, int64_t out[4]);
+
 /* tensor export/import for --dumpmatrix (gretel/cmd.py:81-82) and tests:
  * band layout [(N+2)][band][7][7] as doubles; dense layout [7][7][N+2][N+2] (gretel/cmd.py:76-77). */
 int gh_export_band(gh_t *h, double *out);
