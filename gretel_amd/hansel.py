@@ -172,7 +172,7 @@ class Hansel:
 
     @property
     def n_slices(self):
-        return int(self._get_stats().n_slices) if self._h is not None else getattr(self, "_n_slices", 0)
+        return int(self._get_stats().n_slices) if self._h is not None else 0
 
     @n_slices.setter
     def n_slices(self, v):
@@ -183,7 +183,8 @@ class Hansel:
 
     @property
     def n_crumbs(self):
-        return int(self._get_stats().n_crumbs) if self._h is not None else len(self._staged)
+        # (an attribute that only its setter and the fused fill write, like the reference's: staging an observation leaves it)
+        return int(self._get_stats().n_crumbs) if self._h is not None else 0
 
     @n_crumbs.setter
     def n_crumbs(self, v):

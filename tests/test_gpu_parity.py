@@ -135,7 +135,8 @@ def test_fill_rejects_bad_symbols_and_band_overflow():
 
 
 # -- lookups ----------------------------------------------------------------------------------------
-@pytest.mark.parametrize("storage,mode,mt", [("f32", "A", False), ("f32", "B", True), ("f32", "C", False), ("f32", "D", False), ("f64", "A", True)])
+@pytest.mark.parametrize("storage,mode,mt", [("f32", "A", False), ("f32", "B", True), ("f32", "C", False), ("f32", "D", False), ("f64", "A", True),
+                                            ("f32", "E", False), ("f64", "E", True)])
 def test_lookups_match_oracle(storage, mode, mt):
     t = make_support_table(120, 5000, k=5, seed=3)
     h, o = _pair(t, storage, mode, mt)
