@@ -18,6 +18,8 @@ GH_STORAGE = {"f32": 0, "f64": 1}
 GH_COND = {"A": 0, "B": 1, "C": 2, "D": 3, "E": 4}
 GH_BEAM_MAX = 32
 GH_K = {"fill": 0, "marg": 1, "lt": 2, "walk": 3, "reweight": 4, "seg": 5, "rwseg": 6}
+GH_FLOW = {0: "none", 1: "serial", 2: "seg", 3: "rwseg", 4: "fuse", 5: "pools"}      # gh_spin_plan.flow
+GH_WALK = {"seg": 0, "spec": 1, "spec1": 2, "src": 3}                                # gh_spin_plan_in.walk_mode
 
 
 class GretelHipError(RuntimeError):
@@ -59,6 +61,22 @@ class gh_score_rec(C.Structure):
     _fields_ = [("ll_chain", C.c_double), ("hp_current", C.c_double), ("hp_original", C.c_double), ("min_marginal", C.c_double),
                 ("min_margin", C.c_double), ("n_on", C.c_int32), ("n_greedy", C.c_int32), ("first_off", C.c_int32),
                 ("argmin_margin", C.c_int32)]
+
+
+class gh_spin_plan_in(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in (
+        "n_snps", "band", "L", "storage", "cond_mode", "marginal_term", "offer_zero", "walk_mode", "lt_full", "need_rinfo",
+        "pools_off", "ranked", "rwseg", "rwseg_small", "emit_small", "fuse", "seg6", "mixed", "rw_lp16", "rw_tband")]
+
+
+class gh_spin_plan(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("flow", "emit_small", "seg6", "stride", "rw_lanes", "S", "mixed", "need_layout")] + [
+        ("lds", C.c_int64)]
+
+    def as_dict(self):
+        d = {n: int(getattr(self, n)) for n, _ in self._fields_}
+        d["flow"] = GH_FLOW[d["flow"]]
+        return d
 
 
 _lib = None
@@ -132,6 +150,8 @@ def load():
         "gh_profile_overhead": [vp, i32, vp],
         "gh_debug_walk_clock": [vp, vp],
         "gh_debug_pool_geometry": [i32, i32, i32, vp],
+        "gh_debug_spin_plan": [P(gh_spin_plan_in), P(gh_spin_plan)],
+        "gh_debug_last_spin_plan": [vp, P(gh_spin_plan)],
         "gh_assign_reads": [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, P(gh_assign_stats)],
         "gh_score_paths": [vp, vp, i32, vp, vp, vp, vp],
         "gh_beam_paths": [vp, i32, vp, vp, P(i32), P(i32)],
@@ -156,6 +176,25 @@ def check(rc):
     if rc == GH_ERR_SYMBOL:
         raise SymbolError(rc, msg)
     raise GretelHipError(rc, msg)
+
+
+def spin_plan(n_snps, band, L, storage="f32", cond_mode="A", marginal_term=False, offer_zero=False, walk="seg", lt_full=False,
+              need_rinfo=None, pools_off=False, ranked=-1, **switches):
+    """Which kernels a gh_spin of such a window would run for every path (gh_debug_spin_plan: no handle, no GPU), as a dict.
+    switches: rwseg, rwseg_small, emit_small, fuse, seg6, mixed, rw_lp16, rw_tband -- the value of GH_<NAME>, unset when left out.
+    need_rinfo defaults to what gh_create makes of marginal_term and fuse."""
+    names = ("rwseg", "rwseg_small", "emit_small", "fuse", "seg6", "mixed", "rw_lp16", "rw_tband")
+    bad = set(switches) - set(names)
+    if bad:
+        raise TypeError("spin_plan: unknown switches %s" % sorted(bad))
+    if need_rinfo is None:
+        need_rinfo = bool(marginal_term) or switches.get("fuse", 0) >= 1
+    inp = gh_spin_plan_in(int(n_snps), int(band), int(L), GH_STORAGE[storage], GH_COND[cond_mode], int(marginal_term), int(offer_zero),
+                          GH_WALK[walk], int(lt_full), int(need_rinfo), int(pools_off), int(ranked),
+                          *[int(switches.get(n, -1)) for n in names])
+    out = gh_spin_plan()
+    check(load().gh_debug_spin_plan(C.byref(inp), C.byref(out)))
+    return out.as_dict()
 
 
 def device_clock_khz(device=-1):

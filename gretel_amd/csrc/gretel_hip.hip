@@ -146,15 +146,12 @@ struct gh_handle {
     double *seg_smin, *seg_gmin;   // minimum marginal per (segment, entry state) / per (group, entry state)
     size_t seg_smin_bytes;
     uint8_t *cm5snap;      // [N+2] candidate bits as the last k_seg saw them
-    size_t fuse_lds;       // LDS of k_rw's fused prologue for this spin's state space
     bool band_zero = true; // the tensor holds nothing but zeros (gh_create, gh_clear; until something is added): k_fill_own may store instead of add
     void *tband;           // column conditionals, lane groups of 16 / 32: the band once more, TO-major (tband[bidx(W, p, d, b, a)] = band[bidx(W, p, d, a, b)])
     bool lt_inc_seg;       // lt_inc_path was left by a reweight behind a segment-parallel walk (k_rw / k_rwseg keep the table under every conditional)
     uint64_t band_epoch = 1, tband_epoch;  // tband mirrors the band iff equal: everything that writes the band counts, k_rw<.., COL> keeps both
     void *seg_halo;        // k_rwseg: per segment, the band blocks of the L positions in front of it (k_emit's copy)
     size_t seg_halo_bytes;
-    bool rws;              // inside a gh_spin whose paths run as k_rwseg + k_scan + k_emit (segwalk.hpp)
-    bool fuse;             // inside a gh_spin over the enumerated states: no k_emit, k_rw chains the maps itself (segwalk.hpp)
     double *lmsel1;        // [N+1] selected log-marginals of a lone gh_generate_path
     double *spin_lmsel;    // [spin_cap][N+1] the same for every path of a spin
     int seg_L;
@@ -171,7 +168,6 @@ struct gh_handle {
     bool cw_off;           // a position with five candidates and more than CW_MAX_L5 lags: serial walkers only
     bool cw_wide;          // the conditional table is over the symbols, not over candidate ranks: k_cwalk<L, 5>
     bool cw_pool_wide;     // ... and what the pools' states are made of
-    bool cw_no_rw;         // inside gh_generate_path: no reweight follows the path (k_cemit leaves the window's flags standing)
     uint8_t *cw_keys_d, *cw_exits_d, *cw_pend_d;      // k_cwalkg: the states as bytes, [S][CW_K][cw_LD] (cw_pend_d: two sets, as the request lists)
     uint8_t *cw_pend_exit_d;                          // ... and the exit states run-on requests arrive with, two sets
     int cw_LD;
@@ -191,9 +187,8 @@ struct gh_handle {
     void *beam_buf;        // gh_beam_paths / gh_beam_spin (beam.hpp): the beam's own table, back-pointers, path rows and scores; grows with N * L
     size_t beam_cap;
     int64_t beam_last[4];  // gh_beam_info: the last beam run on this handle
-    bool seg6;            // inside a gh_spin at L = 6 whose table is ranked: every state of every segment (4^6), not pools
     int cw_round_cap = env_int("GH_CW_ROUND_CAP", 0);   // =k at creation (tests): never more than k rounds per launch, so that chains stay open and the serial fallback runs
-    int spin_partial_stride;   // doubles between two paths' partial sums of the removed mass in a spin (0 outside spins)
+    gh_spin_plan last_plan;    // what the last gh_spin ran with (gh_debug_last_spin_plan; nothing else reads it)
     int spin_requeues;     // how often the last gh_spin rebuilt the table and queued the remaining paths again
     gh_fill_stats stats = {0, 0, 0, 1, 0};
     int wmode = walk_mode_from_env();        // WM_*: which path extension (GH_WALK at creation)
@@ -983,15 +978,13 @@ static bool seg_ok(int wm, int L);
 // derived = false (the candidate pools' looks): the depth-2 serial walker's tables Ht / Yt are left alone -- nobody reads them
 // until a serial walk, in front of which the table is rebuilt in full anyway (45 us per look at C5 otherwise)
 // the mixed-radix state space (segmix.hpp) for this handle?  L = 5 over the segment-parallel extension; not where every symbol is
-// offered everywhere (five candidates at every position: nothing to gain) and not inside a spin of the opt-in GH_FUSE flow, whose
-// k_seg / k_scan / k_rw carry the minima over the enumerated states
-static bool mixed_allowed(const gh_handle *h)
-{
-    static const bool off = env_off("GH_MIXED");
-    return !off && !h->fuse && h->L == SEGM_L && h->wmode == WM_SEG && !h->cfg.offer_zero;
-}
+// offered everywhere (five candidates at every position: nothing to gain) and not for a spin of the opt-in GH_FUSE flow
+// (`enumerated`; false outside spins), whose k_seg / k_scan / k_rw carry the minima over the enumerated states
+static bool mixed_ok(bool on, bool enumerated, int L, int wm, int offer_zero) { return on && !enumerated && L == SEGM_L && wm == WM_SEG && !offer_zero; }
+static bool mixed_on() { static const bool on = !env_off("GH_MIXED"); return on; }      // (read once per process)
+static bool mixed_allowed(const gh_handle *h, bool enumerated) { return mixed_ok(mixed_on(), enumerated, h->L, h->wmode, h->cfg.offer_zero); }
 
-static int ensure_lt(gh_handle *h, bool baked = false, bool derived = true)
+static int ensure_lt(gh_handle *h, bool baked = false, bool derived = true, bool enumerated = false)
 {
     int rc = ensure_marg(h);
     if (rc) return rc;
@@ -1027,7 +1020,7 @@ static int ensure_lt(gh_handle *h, bool baked = false, bool derived = true)
     { int rc_ = post_launch(h, "k_lt"); if (rc_) return rc_; }
     // mixed radix for the segment-parallel extension (segmix.hpp): how many states enter a target at most, taken whenever the table
     // may have been rebuilt (k_lt zeroes it then; behind an incremental refresh the old bound stands: candidates only disappear)
-    if (mixed_allowed(h)) {
+    if (mixed_allowed(h, enumerated)) {
         hipLaunchKernelGGL(k_classify, dim3((unsigned)((h->N + 255) / 256)), dim3(256), 0, h->stream, (const uint32_t *)h->cmask, h->N, h->L, h->dstate);
         int rc_ = post_launch(h, "k_classify"); if (rc_) return rc_;
     }
@@ -1297,83 +1290,83 @@ static seg_params seg_make_params(const gh_handle *h, int rearm, int check_masks
     return P;
 }
 
+typedef gh_spin_plan spin_plan;       // which kernels run for every path of a spin (plan_spin); value-initialised: outside a spin
+
+// segments / groups the launches over the enumerated states are cut into
+static int seg_S(int N, int L) { return (int)max_cls(L, [&](int R) { return (size_t)seg_geometry(N, L, R).S; }); }
+static int seg_G1(int N, int L) { return (int)max_cls(L, [&](int R) { return (size_t)seg_geometry(N, L, R).G1; }); }
+// short memories / small windows: every segment map fits the LDS of the emitting workgroup (k_emit_small).  sw: GH_EMIT_SMALL, -1 = unset
+static bool emit_small_ok(int N, int L, int sw) { return sw != 0 && max_cls(L, [&](int R) { return emit_small_lds_bytes(N, L, R); }) <= 64 * 1024; }
+
+// what follows the first kernel of a path: k_emit_small alone (behind k_rwseg it takes k_scan's look at what the reweight found as
+// well: two launches per path), else k_scan + k_emit
 template <int LC>
-static void launch_seg_lc(gh_handle *h, const seg_params &P)
+static void launch_emit_tail(gh_handle *h, const spin_plan &plan, const seg_params &P)
 {
-    hipStream_t stream = h->stream;
-    const int N = h->N, dev = h->dev;
-    const size_t lds_seg = max_cls(LC, [&](int R) { return seg_lds_total(R, LC); });
+    const int N = h->N, S = seg_S(N, LC);
+    if (plan.emit_small) {
+        const size_t lds_small = max_cls(LC, [&](int R) { return emit_small_lds_bytes(N, LC, R); });
+        lds_limit<k_emit_small<LC>>(lds_small, h->dev);
+        hipLaunchKernelGGL((k_emit_small<LC>), dim3(S), dim3(SEG_THREADS), lds_small, h->stream, P);
+        return;
+    }
     const size_t lds_scan = max_cls(LC, [&](int R) { return scan_lds_bytes(N, LC, R); });
     const size_t lds_emit = max_cls(LC, [&](int R) { return emit_lds_bytes(N, LC, R); });
-    const int S = (int)max_cls(LC, [&](int R) { return (size_t)seg_geometry(N, LC, R).S; }), G1 = (int)max_cls(LC, [&](int R) { return (size_t)seg_geometry(N, LC, R).G1; });
-    if (h->fuse) {
-        // spins without k_emit: k_seg / k_scan also carry the minimum marginals (TRACK), k_rw chains the group maps itself
-        lds_limit<k_seg<LC, true>>(lds_seg, dev);
-        lds_limit<k_scan<LC, true>>(lds_scan, dev);
-        prof_begin(h, GH_K_SEG);
-        hipLaunchKernelGGL((k_seg<LC, true>), dim3(S), dim3(SEG_THREADS), lds_seg, stream, P);
-        prof_end(h, GH_K_SEG, (double)N * (double)LC * CELL * esize(h));
-        hipLaunchKernelGGL((k_scan<LC, true>), dim3(G1), dim3(SEG_THREADS), lds_scan, stream, P);
-        return;
-    }
-    lds_limit<k_seg<LC, false>>(lds_seg, dev);
-    lds_limit<k_scan<LC, false>>(lds_scan, dev);
-    lds_limit<k_emit<LC>>(lds_emit, dev);
-    prof_begin(h, GH_K_SEG);
-    hipLaunchKernelGGL((k_seg<LC, false>), dim3(S), dim3(SEG_THREADS), lds_seg, stream, P);
-    // algorithmic bytes of k_seg: the conditional lookups of the extension (SURVEY 8(d): L history cells per step)
-    prof_end(h, GH_K_SEG, (double)N * (double)LC * CELL * esize(h));
-    // short memories / small windows: every segment map fits the LDS of the emitting workgroup, which composes them itself
-    const size_t lds_small = max_cls(LC, [&](int R) { return emit_small_lds_bytes(N, LC, R); });
-    static const bool no_small = env_off("GH_EMIT_SMALL");
-    if (lds_small <= 64 * 1024 && !no_small) {
-        lds_limit<k_emit_small<LC>>(lds_small, dev);
-        hipLaunchKernelGGL((k_emit_small<LC>), dim3(S), dim3(SEG_THREADS), lds_small, stream, P);
-        return;
-    }
-    hipLaunchKernelGGL((k_scan<LC, false>), dim3(G1), dim3(SEG_THREADS), lds_scan, stream, P);
-    hipLaunchKernelGGL((k_emit<LC>), dim3(S), dim3(SEG_THREADS), lds_emit, stream, P);
+    lds_limit<k_scan<LC, false>>(lds_scan, h->dev);
+    lds_limit<k_emit<LC>>(lds_emit, h->dev);
+    hipLaunchKernelGGL((k_scan<LC, false>), dim3(seg_G1(N, LC)), dim3(SEG_THREADS), lds_scan, h->stream, P);
+    hipLaunchKernelGGL((k_emit<LC>), dim3(S), dim3(SEG_THREADS), lds_emit, h->stream, P);
 }
 
-static int launch_seg_walk(gh_handle *h, uint8_t *d_path, double *d_lmsel, int rearm, int check_masks)
+template <int LC, bool TRACK>
+static void launch_seg_first(gh_handle *h, const seg_params &P)
+{
+    const size_t lds_seg = max_cls(LC, [&](int R) { return seg_lds_total(R, LC); });
+    lds_limit<k_seg<LC, TRACK>>(lds_seg, h->dev);
+    prof_begin(h, GH_K_SEG);
+    hipLaunchKernelGGL((k_seg<LC, TRACK>), dim3(seg_S(h->N, LC)), dim3(SEG_THREADS), lds_seg, h->stream, P);
+    // algorithmic bytes of k_seg: the conditional lookups of the extension (SURVEY 8(d): L history cells per step)
+    prof_end(h, GH_K_SEG, (double)h->N * (double)LC * CELL * esize(h));
+}
+
+template <int LC>
+static void launch_seg_lc(gh_handle *h, const spin_plan &plan, const seg_params &P)
+{
+    if (plan.flow != GH_FLOW_FUSE) { launch_seg_first<LC, false>(h, P); launch_emit_tail<LC>(h, plan, P); return; }
+    // spins without k_emit: k_seg / k_scan also carry the minimum marginals (TRACK), k_rw chains the group maps itself
+    const size_t lds_scan = max_cls(LC, [&](int R) { return scan_lds_bytes(h->N, LC, R); });
+    lds_limit<k_scan<LC, true>>(lds_scan, h->dev);
+    launch_seg_first<LC, true>(h, P);
+    hipLaunchKernelGGL((k_scan<LC, true>), dim3(seg_G1(h->N, LC)), dim3(SEG_THREADS), lds_scan, h->stream, P);
+}
+
+static int launch_seg_walk(gh_handle *h, const spin_plan &plan, uint8_t *d_path, double *d_lmsel, int rearm, int check_masks)
 {
     int rc = alloc_seg(h);
     if (rc) return rc;
     seg_params P = seg_make_params(h, rearm, check_masks, d_path, d_lmsel ? d_lmsel : h->lmsel1);      // (lmsel1 exists only behind alloc_seg)
-    P.halo = h->rws ? h->seg_halo : nullptr;
+    P.halo = plan.flow == GH_FLOW_RWSEG ? h->seg_halo : nullptr;
     if (h->L < 1 || h->L > SEG_MAX_L_NARROW) return fail(GH_ERR_STATE, "segment-parallel walk needs L <= %d", SEG_MAX_L_NARROW);
     prof_begin(h, GH_K_WALK);
     switch (h->L) {
-        case 1: launch_seg_lc<1>(h, P); break;
-        case 2: launch_seg_lc<2>(h, P); break;
-        case 3: launch_seg_lc<3>(h, P); break;
-        case 4: launch_seg_lc<4>(h, P); break;
-        case 5: launch_seg_lc<5>(h, P); break;
-        case 6: launch_seg_lc<6>(h, P); break;      // (ranked tables only: gh_spin decides)
+#define SEG_CASE(n) case n: launch_seg_lc<n>(h, plan, P); break;
+        SEG_CASE(1) SEG_CASE(2) SEG_CASE(3) SEG_CASE(4) SEG_CASE(5) SEG_CASE(6)      // (6: ranked tables only, plan_spin decides)
+#undef SEG_CASE
     }
     prof_end(h, GH_K_WALK, walk_bytes(h->N, h->L, esize(h)));
     return post_launch(h, "k_seg/k_scan/k_emit");
 }
 
 // ---- k_rwseg: reweight of the path before + this path's k_seg in one launch, then k_scan, k_emit (segwalk.hpp) ----------
-static size_t rws_lds_bytes(int LC, bool five)
+// where the patch lies in k_rwseg's dynamic LDS (behind k_seg's regions for either radix and, under the column conditionals,
+// behind the staged band blocks of the workgroup's positions); the kernel needs this + sizeof(seg_patch).  es: bytes per element
+static size_t rws_patch_off(int N, int W, int LC, bool col, size_t es)
 {
-    (void)five;
-    size_t b = max_cls(LC, [&](int R) { return seg_lds_total(R, LC); });
-    if (b < (size_t)SEG_THREADS * 8) b = (size_t)SEG_THREADS * 8;      // the reweight phase's reduction scratch
-    return (b + 15) & ~(size_t)15;
-}
-
-// where the patch lies in k_rwseg's dynamic LDS for this handle (behind k_seg's regions for either radix and, under the column
-// conditionals, behind the staged band blocks of the workgroup's positions); the kernel needs this + sizeof(seg_patch)
-static size_t rws_patch_off(const gh_handle *h, int LC)
-{
-    const bool five = seg_radix_ok(5, LC);
-    const seg_geom g4 = seg_geometry(h->N, LC, 4), g5 = five ? seg_geometry(h->N, LC, 5) : g4;
-    size_t off = rws_lds_bytes(LC, five);
-    if (h->cfg.cond_mode == GH_COND_C || h->cfg.cond_mode == GH_COND_E) {
-        const int longest = g4.seglen > g5.seglen ? g4.seglen : g5.seglen;
-        const size_t need = (size_t)SEG_THREADS * 8 + (size_t)(longest + LC + 1) * NSYM * h->W * NSYM * esize(h);
+    size_t off = max2(max_cls(LC, [&](int R) { return seg_lds_total(R, LC); }), (size_t)SEG_THREADS * 8);      // (the reweight phase's reduction scratch)
+    off = (off + 15) & ~(size_t)15;
+    if (col) {
+        const int longest = (int)max_cls(LC, [&](int R) { return (size_t)seg_geometry(N, LC, R).seglen; });
+        const size_t need = (size_t)SEG_THREADS * 8 + (size_t)(longest + LC + 1) * NSYM * W * NSYM * es;
         if (need > off) off = (need + 15) & ~(size_t)15;
     }
     return off;
@@ -1381,39 +1374,20 @@ static size_t rws_patch_off(const gh_handle *h, int LC)
 #define RWS_LDS_MAX (160 * 1024 - 3 * 1024 - 512)      /* what a workgroup may have of the CU's 160 KB, less the kernel's static variables */
 
 template <typename T, int LC, bool COL>
-static void launch_rwseg_lc(gh_handle *h, seg_params P, const rws_params &Q)
+static void launch_rwseg_lc(gh_handle *h, const spin_plan &plan, seg_params P, const rws_params &Q)
 {
-    constexpr bool five = seg_radix_ok(5, LC);
-    const int N = h->N;
-    (void)five;
-    const int S = (int)max_cls(LC, [&](int R) { return (size_t)seg_geometry(N, LC, R).S; }), G1 = (int)max_cls(LC, [&](int R) { return (size_t)seg_geometry(N, LC, R).G1; });
-    const size_t off = rws_patch_off(h, LC);
-    const size_t lds = off + sizeof(seg_patch);
-    const size_t lds_scan = max_cls(LC, [&](int R) { return scan_lds_bytes(N, LC, R); });
-    const size_t lds_emit = max_cls(LC, [&](int R) { return emit_lds_bytes(N, LC, R); });
+    const size_t lds = (size_t)plan.lds;
     lds_limit<k_rwseg<T, LC, COL>>(lds, h->dev);
-    lds_limit<k_scan<LC, false>>(lds_scan, h->dev);
-    lds_limit<k_emit<LC>>(lds_emit, h->dev);
-    P.patch_off = (int)off;
-    P.rws = 1;
+    P.patch_off = (int)(lds - sizeof(seg_patch));
     prof_begin(h, GH_K_RWSEG);
-    hipLaunchKernelGGL((k_rwseg<T, LC, COL>), dim3(S), dim3(SEG_THREADS), lds, h->stream, P, Q);
+    hipLaunchKernelGGL((k_rwseg<T, LC, COL>), dim3(seg_S(h->N, LC)), dim3(SEG_THREADS), lds, h->stream, P, Q);
     // the extension's conditional lookups + what the reweight of a path reads and writes (the figure GH_K_REWEIGHT quotes)
-    prof_end(h, GH_K_RWSEG, (double)N * (double)LC * CELL * esize(h) + reweight_bytes(N, h->W, LC, esize(h), true));
-    // short memories / small windows: every segment map fits the LDS of the emitting workgroup, which composes them itself and
-    // takes k_scan's look at what the reweight found as well: two launches per path
-    const size_t lds_small = max_cls(LC, [&](int R) { return emit_small_lds_bytes(N, LC, R); });
-    if (lds_small <= 64 * 1024 && !env_off("GH_EMIT_SMALL")) {
-        lds_limit<k_emit_small<LC>>(lds_small, h->dev);
-        hipLaunchKernelGGL((k_emit_small<LC>), dim3(S), dim3(SEG_THREADS), lds_small, h->stream, P);
-        return;
-    }
-    hipLaunchKernelGGL((k_scan<LC, false>), dim3(G1), dim3(SEG_THREADS), lds_scan, h->stream, P);
-    hipLaunchKernelGGL((k_emit<LC>), dim3(S), dim3(SEG_THREADS), lds_emit, h->stream, P);
+    prof_end(h, GH_K_RWSEG, (double)h->N * (double)LC * CELL * esize(h) + reweight_bytes(h->N, h->W, LC, esize(h), true));
+    launch_emit_tail<LC>(h, plan, P);
 }
 
 // reweights along d_prev (record d_prev_rec, removed mass into slot prev_slot) and walks the next path into d_path
-static int launch_rwseg(gh_handle *h, const uint8_t *d_prev, gh_path_rec *d_prev_rec, int prev_slot, double min_remove,
+static int launch_rwseg(gh_handle *h, const spin_plan &plan, const uint8_t *d_prev, gh_path_rec *d_prev_rec, int prev_slot, double min_remove,
                         uint8_t *d_path, double *d_lmsel, int check_masks)
 {
     int rc = alloc_seg(h);
@@ -1423,7 +1397,7 @@ static int launch_rwseg(gh_handle *h, const uint8_t *d_prev, gh_path_rec *d_prev
     rws_params Q;
     Q.band = h->band; Q.cnt = h->cnt; Q.marg = h->marg; Q.minfo = h->minfo; Q.rinfo = h->need_rinfo ? h->rinfo : nullptr; Q.G = h->lt;
     Q.nvalid = h->nvalid; Q.cmask = h->cmask; Q.path = d_prev; Q.min_remove = min_remove;
-    Q.partial = h->partial + (size_t)prev_slot * h->spin_partial_stride;
+    Q.partial = h->partial + (size_t)prev_slot * plan.stride;
     Q.rec = d_prev_rec; Q.cond_mode = h->cfg.cond_mode; Q.offer_zero = h->cfg.offer_zero;
     if (h->L < 1 || h->L > SEG_MAX_L_NARROW) return fail(GH_ERR_STATE, "k_rwseg needs L <= %d", SEG_MAX_L_NARROW);   // before the bracket opens
     prof_begin(h, GH_K_WALK);
@@ -1431,7 +1405,7 @@ static int launch_rwseg(gh_handle *h, const uint8_t *d_prev, gh_path_rec *d_prev
     with_storage(h, [&](auto z) {
         using T = decltype(z);
         switch (h->L) {
-#define RWS_CASE(n) case n: if (col) launch_rwseg_lc<T, n, true>(h, P, Q); else launch_rwseg_lc<T, n, false>(h, P, Q); break;
+#define RWS_CASE(n) case n: if (col) launch_rwseg_lc<T, n, true>(h, plan, P, Q); else launch_rwseg_lc<T, n, false>(h, plan, P, Q); break;
             RWS_CASE(1) RWS_CASE(2) RWS_CASE(3) RWS_CASE(4) RWS_CASE(5) RWS_CASE(6)
 #undef RWS_CASE
         }
@@ -1448,10 +1422,10 @@ static int launch_rwseg(gh_handle *h, const uint8_t *d_prev, gh_path_rec *d_prev
 
 // serial walkers: the record is closed by the walker itself.  Segment-parallel: by the k_marg<T,true> that follows
 // (spins) or by k_seg_fin (lone gh_generate_path); d_lmsel receives the selected log-marginals for k_hp.
-static int launch_walk(gh_handle *h, uint8_t *d_path, gh_path_rec *d_rec, double min_remove, int rearm, double *d_lmsel = nullptr,
-                       int check_masks = 0)
+static int launch_walk(gh_handle *h, const spin_plan &plan, uint8_t *d_path, gh_path_rec *d_rec, double min_remove, int rearm,
+                       double *d_lmsel = nullptr, int check_masks = 0)
 {
-    if (seg_ok(h->wmode, h->L) || h->seg6) return launch_seg_walk(h, d_path, d_lmsel, rearm, check_masks);
+    if (seg_ok(h->wmode, h->L) || plan.seg6) return launch_seg_walk(h, plan, d_path, d_lmsel, rearm, check_masks);
     walk_params P;
     P.N = h->N; P.L = h->L; P.chunk = 0; P.rearm = rearm;
     P.G = h->lt; P.Ht = h->ht; P.Yt = h->yt; P.minfo = h->minfo;
@@ -1459,8 +1433,7 @@ static int launch_walk(gh_handle *h, uint8_t *d_path, gh_path_rec *d_rec, double
     prof_begin(h, GH_K_WALK);
     launch_walk_any(h->wmode, h->N, h->L, P, h->stream, 1, nullptr, 0);
     prof_end(h, GH_K_WALK, walk_bytes(h->N, h->L, esize(h)));
-    { int rc_ = post_launch(h, "k_walk"); if (rc_) return rc_; }
-    return GH_OK;
+    return post_launch(h, "k_walk");
 }
 
 // reweight along d_path AND refresh the marginal tables in one pass (k_marg<T, true>)
@@ -1478,8 +1451,6 @@ static int ensure_partial(gh_handle *h, int nb, int slots)
     return GH_OK;
 }
 
-// slot < 0: reduce the removed mass right behind the pass (k_reweight_finish).  slot >= 0 (gh_spin): keep this
-// path's partial sums in their own slot, the caller reduces all paths with one k_reweight_finish_all at the end.
 // k_rw's lane group: 32 lanes per position where the band or the lag count exceeds 8 (all distances and lags in one
 // round), else 8; blocks per path accordingly (also the stride of the per-path partial sums of the removed mass)
 // (16: row conditionals with bands up to 32 and at most 16 lags -- the distances beyond 16 take a second round, the table
@@ -1500,38 +1471,49 @@ static int ensure_tband(gh_handle *h, hipStream_t st)
 
 static bool rw_col(const gh_handle *h) { return h->cfg.cond_mode == GH_COND_C || h->cfg.cond_mode == GH_COND_E; }
 // column conditionals beyond the 8-lane groups: k_rw reads its columns from a to-major copy of the band (GH_RW_TBAND=0: from the staged block)
-static bool rw_tband(const gh_handle *h)
+static bool rw_tband_on() { static const bool on = !env_off("GH_RW_TBAND"); return on; }      // (both read once per process)
+static bool rw_lp16_on() { static const bool on = !env_off("GH_RW_LP16"); return on; }
+static bool rw_tband(const gh_handle *h) { return rw_col(h) && (h->W > 8 || h->L > 8) && rw_tband_on(); }
+static int rw_lanes_of(int W, int L, bool col, bool lp16, bool tband)
 {
-    static const bool off = env_off("GH_RW_TBAND");
-    return rw_col(h) && (h->W > 8 || h->L > 8) && !off;
+    if (!(W > 8 || L > 8)) return 8;
+    return (W <= 32 && L <= 16 && lp16 && (!col || tband)) ? 16 : 32;
 }
-static int rw_lanes(const gh_handle *h)
-{
-    if (!(h->W > 8 || h->L > 8)) return 8;
-    static const bool no16 = env_off("GH_RW_LP16");
-    return (h->W <= 32 && h->L <= 16 && !no16 && (!rw_col(h) || rw_tband(h))) ? 16 : 32;
-}
-static int rw_blocks(const gh_handle *h, bool seg) { return (int)(((size_t)(h->N + 1) * (seg ? rw_lanes(h) : 8) + 255) / 256); }
+static int rw_lanes(const gh_handle *h) { return rw_lanes_of(h->W, h->L, rw_col(h), rw_lp16_on(), rw_tband_on()); }
+static int rw_blocks_of(int N, int lanes) { return (int)(((size_t)(N + 1) * lanes + 255) / 256); }
+static int rw_blocks(const gh_handle *h, bool seg) { return rw_blocks_of(h->N, seg ? rw_lanes(h) : 8); }
 
-// seg: the walk just before was segment-parallel: the kernel reduces the minimum marginal itself, clamps it to `ratio`
-// (= min_remove) and closes the record
-static int launch_reweight_marg(gh_handle *h, const uint8_t *d_path, double ratio, int use_state, gh_path_rec *d_rec, int slot = -1,
-                                bool seg = false, bool chained = false, int nseg_arg = 0, double *d_lmsel = nullptr)
+struct rw_req {
+    const uint8_t *path;        // the path to reweight along, and its record
+    gh_path_rec *rec;
+    double ratio = 0.0;         // what to remove (seg: min_remove)
+    int use_state = 1;          // the ratio is the one the walker left in the window's state (0: a lone reweight by `ratio`)
+    int slot = -1;              // < 0: reduce the removed mass right behind the pass (k_reweight_finish); >= 0 (gh_spin): this path's partial
+                                // sums in their own slot, the caller reduces all paths with one k_reweight_finish_all at the end
+    bool seg = false;           // behind a segment-parallel walk: the kernel reduces the minimum marginal itself, clamps it to `ratio`, closes the record
+    bool chained = false;       // a spin without k_lt between its paths (below)
+    int nseg = 0;               // segments of a candidate-pool walk whose minima the kernel reduces (0: the enumerated states)
+    double *lmsel = nullptr;    // the three-launch flow: where k_rw writes the selected log-marginals
+};
+static int launch_reweight_marg(gh_handle *h, const spin_plan &plan, const rw_req &q)
 {
-    const int block = 256;
+    const int use_state = q.use_state, slot = q.slot, block = 256;
+    const bool seg = q.seg;
     const int nb = rw_blocks(h, seg);
-    // (a spin strides its per-path partial sums by the widest kernel it may launch: see gh_spin)
-    const int stride = (slot >= 0 && h->spin_partial_stride > nb) ? h->spin_partial_stride : nb;
+    // (a spin strides its per-path partial sums by the widest kernel it may launch: plan_spin)
+    const int stride = (slot >= 0 && plan.stride > nb) ? plan.stride : nb;
+    // the three-launch flow: behind k_seg + k_scan without a k_emit the kernel finds its picks itself and writes the path to q.path / lmsel
+    const bool fused = plan.flow == GH_FLOW_FUSE && q.nseg == 0;
     if (slot < 0) { int rc_ = ensure_partial(h, nb, 1); if (rc_) return rc_; }
     double *partial = h->partial + (slot > 0 ? (size_t)slot * stride : 0);
-    if (slot >= 0 && stride > nb && !h->rws) HIPCHK(hipMemsetAsync(partial + nb, 0, sizeof(double) * (size_t)(stride - nb), h->stream));
+    if (slot >= 0 && stride > nb && plan.flow != GH_FLOW_RWSEG) HIPCHK(hipMemsetAsync(partial + nb, 0, sizeof(double) * (size_t)(stride - nb), h->stream));
     // in a spin the walker re-armed the flags when it finished; a lone reweight does it here
     if (!use_state) hipLaunchKernelGGL(k_rearm, dim3(1), dim3(64), 0, h->stream, h->dstate, (const win_desc *)nullptr, 0);
     // with a valid conditional table (conditional A or B, no marginal term) the kernel also rewrites the table rows
     // this path changes; k_lt then only has to confirm that no candidate mask moved
     // (chained: a spin without k_lt between its paths -- the table is current up to the rows the previous reweight rewrote, and
     // the k_seg that ran before this reweight has checked the candidate masks)
-    const bool lt_ok = (!h->dirty_lt || chained) && h->lt && h->lt_L == h->L && (seg ? rw_incremental_ok(h) : lt_incremental_ok(h));
+    const bool lt_ok = (!h->dirty_lt || q.chained) && h->lt && h->lt_L == h->L && (seg ? rw_incremental_ok(h) : lt_incremental_ok(h));
     double *lt_rows = lt_ok ? h->lt : nullptr;
     prof_begin(h, GH_K_REWEIGHT);
     if (seg) {
@@ -1539,16 +1521,14 @@ static int launch_reweight_marg(gh_handle *h, const uint8_t *d_path, double rati
         const bool wide = rw_lanes(h) == 32, mid = rw_lanes(h) == 16;
         const bool col = rw_col(h);                         // the table entries a reweighted cell feeds: a column
         // the to-major copy: made (or made again, when something else wrote the band since) right here, kept by the kernel
-        const bool use_tb = rw_tband(h) && !(h->fuse && nseg_arg == 0);
+        const bool use_tb = rw_tband(h) && !fused;
         if (use_tb) { int rc_ = ensure_tband(h, h->stream); if (rc_) return rc_; }
-        // behind k_seg + k_scan without a k_emit (h->fuse): the kernel finds its picks itself and writes the path to d_path / d_lmsel
         fuse_params fz;
         memset(&fz, 0, sizeof fz);
-        size_t fuse_lds = 0;
-        if (h->fuse && nseg_arg == 0) {
+        const size_t fuse_lds = fused ? (size_t)plan.lds : 0;
+        if (fused) {
             fz.hist = h->seg_hist; fz.pmaps = h->seg_pmaps; fz.gmaps = h->seg_gmaps; fz.gmin = h->seg_gmin; fz.cm5snap = h->cm5snap;
-            fz.path_out = const_cast<uint8_t *>(d_path); fz.lmsel = d_lmsel;
-            fuse_lds = h->fuse_lds;
+            fz.path_out = const_cast<uint8_t *>(q.path); fz.lmsel = q.lmsel;
         }
         with_storage(h, [&](auto z) {
             using T = decltype(z);
@@ -1562,12 +1542,12 @@ static int launch_reweight_marg(gh_handle *h, const uint8_t *d_path, double rati
         const size_t lds_b = fuse_lds + ((stage & 1) ? blk_b : 0);                                                                \
         lds_limit<k_rw<T, LP, COL, FZ>>(lds_b, h->dev);                                                                           \
         hipLaunchKernelGGL((k_rw<T, LP, COL, FZ>), dim3(nb), dim3(block), lds_b, h->stream, (T *)h->band, h->N, h->W, h->cnt, h->marg, h->nvalid, \
-                           h->cmask, h->minfo, h->dstate, d_path, ratio, partial, lt_rows, h->L, h->cfg.cond_mode,                \
-                           (const double *)h->seg_min, d_rec, nseg_arg, h->sm, h->cfg.offer_zero, h->need_rinfo ? h->rinfo : nullptr, stage, fz, (int)fuse_lds, \
+                           h->cmask, h->minfo, h->dstate, q.path, q.ratio, partial, lt_rows, h->L, h->cfg.cond_mode,                \
+                           (const double *)h->seg_min, q.rec, q.nseg, h->sm, h->cfg.offer_zero, h->need_rinfo ? h->rinfo : nullptr, stage, fz, (int)fuse_lds, \
                            (T *)(use_tb ? h->tband : nullptr));                                                                   \
     } while (0)
 #define GH_RW_LAUNCH2(LP) do { if (col) GH_RW_LAUNCH(LP, true, false); else GH_RW_LAUNCH(LP, false, false); } while (0)
-            if (fz.hist) {                                  // (three-launch spins: lane groups of 8 only, gh_spin decides)
+            if (fused) {                                    // (three-launch spins: lane groups of 8 only, plan_spin decides)
                 if (col) GH_RW_LAUNCH(8, true, true); else GH_RW_LAUNCH(8, false, true);
             } else if (mid) GH_RW_LAUNCH2(16);
             else if (wide) GH_RW_LAUNCH2(32);
@@ -1577,21 +1557,21 @@ static int launch_reweight_marg(gh_handle *h, const uint8_t *d_path, double rati
         });
     } else {
         marg_args a = marg_of(h);
-        a.rw_path = d_path; a.ratio = ratio; a.use_state_ratio = use_state; a.partial = partial; a.G = lt_rows; a.L = h->L;
+        a.rw_path = q.path; a.ratio = q.ratio; a.use_state_ratio = use_state; a.partial = partial; a.G = lt_rows; a.L = h->L;
         a.cond_mode = h->cfg.cond_mode;
         launch_marg<true>(h, dim3(nb), h->stream, a);
     }
     if (slot < 0)
-        hipLaunchKernelGGL(k_reweight_finish, dim3(1), dim3(256), 0, h->stream, partial, nb, h->dstate, use_state, d_rec,
+        hipLaunchKernelGGL(k_reweight_finish, dim3(1), dim3(256), 0, h->stream, partial, nb, h->dstate, use_state, q.rec,
                            (const win_desc *)nullptr, 0);
     prof_end(h, GH_K_REWEIGHT, reweight_bytes(h->N, h->W, h->L, esize(h), lt_ok));
     { int rc_ = post_launch(h, "k_marg<reweight>"); if (rc_) return rc_; }
-    h->lt_inc_path = lt_ok ? d_path : nullptr;
+    h->lt_inc_path = lt_ok ? q.path : nullptr;
     h->lt_inc_seg = seg;
     h->dirty_lt = true;
     h->dirty_marg = false;
     h->band_epoch++;
-    if (seg && rw_tband(h) && !(h->fuse && nseg_arg == 0)) h->tband_epoch = h->band_epoch;      // (the kernel wrote both)
+    if (seg && rw_tband(h) && !fused) h->tband_epoch = h->band_epoch;      // (the kernel wrote both)
     return GH_OK;
 }
 
@@ -1677,11 +1657,12 @@ static void cw_pend_sets(const gh_handle *h, const cw_geom &g, cw_params &P)
     }
 }
 
-static cw_params cw_make_params(gh_handle *h, uint8_t *d_path, double *d_lmsel)
+// no_reweight: no reweight follows the path (k_cemit leaves the window's flags standing)
+static cw_params cw_make_params(gh_handle *h, uint8_t *d_path, double *d_lmsel, bool no_reweight)
 {
     cw_params P;
     memset(&P, 0, sizeof P);
-    P.N = h->N; P.L = h->L; P.rearm = h->cw_no_rw ? 0 : 1; P.stamp = h->cw_stamp;
+    P.N = h->N; P.L = h->L; P.rearm = no_reweight ? 0 : 1; P.stamp = h->cw_stamp;
     P.G = h->lt; P.minfo = h->minfo; P.rinfo = h->rinfo; P.mt = h->cfg.marginal_term; P.sm = h->sm; P.st = h->dstate;
     P.keys = h->cw_keys; P.exits = h->cw_exits; P.last_hit = h->cw_last_hit; P.npool = h->cw_npool; P.walked = h->cw_walked; P.nxt = h->cw_nxt; P.pend = h->cw_pend; P.npend = h->cw_npend;
     P.hist = h->cw_hist; P.true_idx = h->cw_true; P.segmin = h->seg_min; P.path_out = d_path; P.lmsel = d_lmsel;
@@ -1728,10 +1709,10 @@ static void launch_cwalkg(const cw_params &P, hipStream_t stream, int S, int dev
 }
 
 // the kernels of one path: `rounds` x (walk what is new, link + chain), emit
-static int launch_cw_path(gh_handle *h, uint8_t *d_path, double *d_lmsel, int rounds, int check_masks, bool resume = false)
+static int launch_cw_path(gh_handle *h, uint8_t *d_path, double *d_lmsel, int rounds, int check_masks, bool no_reweight, bool resume = false)
 {
     const cw_geom g = cw_geometry(h->N, h->L);
-    cw_params P = cw_make_params(h, d_path, d_lmsel);
+    cw_params P = cw_make_params(h, d_path, d_lmsel, no_reweight);
     if (h->cw_round_cap > 0 && rounds > h->cw_round_cap) rounds = h->cw_round_cap;
     const bool skip0 = !resume && !env_off("GH_CW_SKIP0");      // (GH_CW_SKIP0=0: A/B, tests)
     if (!cw_digit_mode(h) && (h->L < CW_MIN_L || h->L > CW_MAX_L)) return fail(GH_ERR_STATE, "candidate-pool walk needs %d <= L <= %d", CW_MIN_L, CW_MAX_LG);
@@ -1789,24 +1770,6 @@ static int launch_cw_path(gh_handle *h, uint8_t *d_path, double *d_lmsel, int ro
     return post_launch(h, "k_cwalk/k_cscan/k_cemit");
 }
 
-// one path through the serial walker, its boundary states into the pools (merge: keep what is there)
-static int cw_serial_path(gh_handle *h, uint8_t *d_path, gh_path_rec *d_rec, double *d_lmsel, double min_remove, int slot, int merge, bool reweight = true)
-{
-    // the serial depth-2 walker reads tables that k_lt keeps; behind pool paths (no k_lt between them) they are stale
-    h->lt_inc_path = nullptr;
-    h->dirty_lt = true;
-    int rc = ensure_lt(h, true);
-    if (rc) return rc;
-    HIPCHK(hipMemsetAsync(d_lmsel, 0, sizeof(double), h->stream));      // k_hp: the walker sums this path itself
-    if ((rc = launch_walk(h, d_path, d_rec, min_remove, 1, nullptr, 0))) return rc;
-    cw_params P = cw_make_params(h, d_path, d_lmsel);
-    const cw_geom g = cw_geometry(h->N, h->L);
-    hipLaunchKernelGGL(k_cseed, dim3((g.S + 255) / 256), dim3(256), 0, h->stream, P, (const uint8_t *)d_path, merge);
-    if ((rc = post_launch(h, "k_cseed"))) return rc;
-    if (reweight) rc = launch_reweight_marg(h, d_path, 0.0, 1, d_rec, slot, false, false, 0);
-    h->cw_stat[1]++;
-    return rc;
-}
 
 // device buffers for the paths, records and selected log-marginals of a spin of max_paths paths
 static int ensure_spin_buffers(gh_handle *h, int max_paths)
@@ -1840,14 +1803,45 @@ struct spin_io {
     int max_paths;
     double min_remove;
     size_t n1;              // bytes per path
-    int nb;                 // stride of the per-path partial sums
-    uint8_t *d_paths;
-    gh_path_rec *d_recs;
+    spin_plan plan;         // (all zero: a lone gh_generate_path)
     uint8_t *paths_out;
     gh_path_rec *recs;
     bool no_reweight;       // gh_generate_path: the path is only recovered (its record closed by k_seg_fin), the tensor stays
 };
 static int spin_candidate_pools(gh_handle *h, const spin_io &io, dev_state &hs, int *first_out, bool *gave_up);
+
+// one path through the serial walker, its boundary states into the pools (merge: keep what is there)
+static int cw_serial_path(gh_handle *h, const spin_io &io, uint8_t *d_path, gh_path_rec *d_rec, double *d_lmsel, int slot, int merge)
+{
+    // the serial depth-2 walker reads tables that k_lt keeps; behind pool paths (no k_lt between them) they are stale
+    h->lt_inc_path = nullptr;
+    h->dirty_lt = true;
+    int rc = ensure_lt(h, true);
+    if (rc) return rc;
+    HIPCHK(hipMemsetAsync(d_lmsel, 0, sizeof(double), h->stream));      // k_hp: the walker sums this path itself
+    if ((rc = launch_walk(h, io.plan, d_path, d_rec, io.min_remove, 1, nullptr, 0))) return rc;
+    cw_params P = cw_make_params(h, d_path, d_lmsel, io.no_reweight);
+    const cw_geom g = cw_geometry(h->N, h->L);
+    hipLaunchKernelGGL(k_cseed, dim3((g.S + 255) / 256), dim3(256), 0, h->stream, P, (const uint8_t *)d_path, merge);
+    if ((rc = post_launch(h, "k_cseed"))) return rc;
+    if (!io.no_reweight) {
+        rw_req q;
+        q.path = d_path; q.rec = d_rec; q.slot = slot;
+        rc = launch_reweight_marg(h, io.plan, q);
+    }
+    h->cw_stat[1]++;
+    return rc;
+}
+
+// what gh_generate_path hands back: where a hole stopped the path, else the closed record
+static void give_record(const dev_state &hs, const gh_path_rec &rec, double *hp_current, double *hp_original, double *min_marginal, int *hole_at)
+{
+    *hole_at = hs.stop ? hs.hole_at : 0;
+    if (hs.stop) return;
+    if (hp_current) *hp_current = rec.hp_current;
+    if (hp_original) *hp_original = rec.hp_original;
+    if (min_marginal) *min_marginal = rec.min_marginal;
+}
 
 extern "C" int gh_generate_path(gh_t *h, const gh_t *original, uint8_t *path_out, double *hp_current,
                                 double *hp_original, double *min_marginal, int *hole_at)
@@ -1870,38 +1864,30 @@ extern "C" int gh_generate_path(gh_t *h, const gh_t *original, uint8_t *path_out
         hipLaunchKernelGGL(k_snapshot, dim3(nb8), dim3(256), 0, h->stream, h->minfo, h->minfo, h->N, (const win_desc *)nullptr);
     }
     if ((rc = reset_spin_state(h))) return rc;
-    if (cw_ok(h->wmode, h->L) && !h->cw_off) {
+    if (pools) {
         // lag counts of the candidate pools: the path comes out of them (one path, no reweight: the tensor stays as it is,
         // the pools keep what they learnt for the next call); only a window they cannot take goes on to the serial walker
         if ((rc = ensure_spin_buffers(h, 1))) return rc;
         gh_path_rec rec1;
-        spin_io io;
-        io.max_paths = 1; io.min_remove = 0.0; io.n1 = (size_t)h->N + 1; io.nb = 0;
-        io.d_paths = h->spin_paths; io.d_recs = h->spin_recs; io.paths_out = path_out; io.recs = &rec1; io.no_reweight = true;
+        spin_io io{};
+        io.max_paths = 1; io.n1 = (size_t)h->N + 1; io.paths_out = path_out; io.recs = &rec1; io.no_reweight = true;
         dev_state hs1;
         memset(&hs1, 0, sizeof hs1);
         int first1 = 0;
         bool gave_up = false;
-        h->cw_no_rw = true;
-        rc = spin_candidate_pools(h, io, hs1, &first1, &gave_up);
-        h->cw_no_rw = false;
-        if (rc) return rc;
+        if ((rc = spin_candidate_pools(h, io, hs1, &first1, &gave_up))) return rc;
         if (!gave_up) {
-            *hole_at = hs1.stop ? hs1.hole_at : 0;
-            if (hs1.stop) {
-                // (the prefix that was walked: the reference returns what it has)
-                HIPCHK(hipMemcpy(path_out, h->spin_paths, (size_t)h->N + 1, hipMemcpyDeviceToHost));
-            } else {
-                if (hp_current) *hp_current = rec1.hp_current;
-                if (hp_original) *hp_original = rec1.hp_original;
-                if (min_marginal) *min_marginal = rec1.min_marginal;
-            }
+            // (a hole: the prefix that was walked -- the reference returns what it has)
+            if (hs1.stop) HIPCHK(hipMemcpy(path_out, h->spin_paths, (size_t)h->N + 1, hipMemcpyDeviceToHost));
+            give_record(hs1, rec1, hp_current, hp_original, min_marginal, hole_at);
             return GH_OK;
         }
         if ((rc = reset_spin_state(h))) return rc;
         if ((rc = ensure_lt(h, true))) return rc;                   // the pools gave the window up: the serial walker's table
     }
-    if ((rc = launch_walk(h, h->d_path, h->d_rec, 0.0, 0))) return rc;
+    spin_plan lone{};                                               // outside a spin: only the tail of the segment-parallel walk is chosen
+    lone.emit_small = seg_ok(h->wmode, h->L) && emit_small_ok(h->N, h->L, env_int("GH_EMIT_SMALL", -1));
+    if ((rc = launch_walk(h, lone, h->d_path, h->d_rec, 0.0, 0))) return rc;
     if (seg_ok(h->wmode, h->L)) {
         // close the record (hole / minimum marginal), then the two likelihood sums
         hipLaunchKernelGGL(k_seg_fin, dim3(1), dim3(256), 0, h->stream, seg_make_params(h, 0, 0, nullptr, nullptr), h->d_rec, 0.0, 0);
@@ -1914,12 +1900,7 @@ extern "C" int gh_generate_path(gh_t *h, const gh_t *original, uint8_t *path_out
     HIPCHK(hipMemcpyAsync(&rec, h->d_rec, sizeof rec, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(path_out, h->d_path, (size_t)h->N + 1, hipMemcpyDeviceToHost, h->stream));
     if ((rc = read_state(h, &hs))) return rc;
-    *hole_at = hs.stop ? hs.hole_at : 0;
-    if (!hs.stop) {
-        if (hp_current) *hp_current = rec.hp_current;
-        if (hp_original) *hp_original = rec.hp_original;
-        if (min_marginal) *min_marginal = rec.min_marginal;
-    }
+    give_record(hs, rec, hp_current, hp_original, min_marginal, hole_at);
     return GH_OK;
 }
 
@@ -1930,7 +1911,9 @@ extern "C" int gh_reweight_path(gh_t *h, const uint8_t *path, double ratio, doub
     for (int q = 0; q <= h->N; q++)
         if (path[q] >= NSYM) return fail(GH_ERR_SYMBOL, "path[%d] = %d is not a symbol index", q, path[q]);
     HIPCHK(hipMemcpyAsync(h->d_rw_path, path, (size_t)h->N + 1, hipMemcpyHostToDevice, h->stream));
-    int rc = launch_reweight_marg(h, h->d_rw_path, ratio, 0, h->d_rec);
+    rw_req q;
+    q.path = h->d_rw_path; q.rec = h->d_rec; q.ratio = ratio; q.use_state = 0;
+    int rc = launch_reweight_marg(h, spin_plan{}, q);
     if (rc) return rc;
     gh_path_rec rec;
     HIPCHK(hipMemcpyAsync(&rec, h->d_rec, sizeof rec, hipMemcpyDeviceToHost, h->stream));
@@ -1939,25 +1922,28 @@ extern "C" int gh_reweight_path(gh_t *h, const uint8_t *path, double ratio, doub
     return GH_OK;
 }
 
+// pinned staging of at least `need` bytes (a new buffer: `cap`); false: no pinned memory to be had
+static bool ensure_stage(gh_handle *h, size_t need, size_t cap)
+{
+    if (need <= h->stage_cap) return true;
+    if (h->stage) hipHostFree(h->stage);
+    h->stage = nullptr; h->stage_cap = 0;
+    if (hipHostMalloc((void **)&h->stage, cap, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); h->stage = nullptr; return false; }
+    h->stage_cap = cap;
+    return true;
+}
+
 // results to the caller's (pageable) buffers through pinned staging: one asynchronous copy each at PCIe rate and a
 // host memcpy, instead of the runtime's chunked pageable path
 static int results_to_host(gh_handle *h, uint8_t *paths_out, const uint8_t *d_paths, size_t path_bytes, gh_path_rec *recs,
                            const gh_path_rec *d_recs, size_t rec_bytes)
 {
     const size_t need = path_bytes + rec_bytes;
-    if (need > h->stage_cap) {
-        if (h->stage) hipHostFree(h->stage);
-        h->stage = nullptr; h->stage_cap = 0;
-        const size_t cap = need + need / 2 + 4096;
-        if (hipHostMalloc((void **)&h->stage, cap, hipHostMallocDefault) != hipSuccess) {
-            // no pinned memory to be had: the plain copies
-            (void)hipGetLastError();
-            h->stage = nullptr;
-            HIPCHK(hipMemcpy(paths_out, d_paths, path_bytes, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(recs, d_recs, rec_bytes, hipMemcpyDeviceToHost));
-            return GH_OK;
-        }
-        h->stage_cap = cap;
+    if (!ensure_stage(h, need, need + need / 2 + 4096)) {
+        // no pinned memory to be had: the plain copies
+        HIPCHK(hipMemcpy(paths_out, d_paths, path_bytes, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(recs, d_recs, rec_bytes, hipMemcpyDeviceToHost));
+        return GH_OK;
     }
     HIPCHK(hipMemcpyAsync(h->stage, d_paths, path_bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(h->stage + path_bytes, d_recs, rec_bytes, hipMemcpyDeviceToHost, h->stream));
@@ -1968,20 +1954,14 @@ static int results_to_host(gh_handle *h, uint8_t *paths_out, const uint8_t *d_pa
 }
 
 // The end of a spin in ONE wait: the device state and the results of the `launched` paths go to pinned staging together
-// (how many of them are complete is only known from the state); stage_deliver then hands n_done of them to the caller.
+// (how many of them are complete is only known from the state); deliver_results then hands n_done of them to the caller.
 // Returns 1 when there is no pinned memory to be had (the caller takes the two-step way).
 static int state_and_results_to_stage(gh_handle *h, dev_state *hs, const uint8_t *d_paths, size_t n1, const gh_path_rec *d_recs, int launched)
 {
     const size_t pb = n1 * (size_t)launched, rb = sizeof(gh_path_rec) * (size_t)launched, need = pb + rb + sizeof(dev_state) + 64;
-    if (need > h->stage_cap) {
-        if (h->stage) hipHostFree(h->stage);
-        h->stage = nullptr; h->stage_cap = 0;
-        // (pinned memory is the dearest allocation of a spin: sized once for what the device buffers hold -- ensure_spin_buffers)
-        const size_t lc = (size_t)(launched > h->spin_cap ? launched : h->spin_cap);
-        const size_t cap = (n1 + sizeof(gh_path_rec)) * lc + sizeof(dev_state) + 64 + 4096;
-        if (hipHostMalloc((void **)&h->stage, cap, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); h->stage = nullptr; return 1; }
-        h->stage_cap = cap;
-    }
+    // (pinned memory is the dearest allocation of a spin: sized once for what the device buffers hold -- ensure_spin_buffers)
+    const size_t lc = (size_t)(launched > h->spin_cap ? launched : h->spin_cap);
+    if (!ensure_stage(h, need, (n1 + sizeof(gh_path_rec)) * lc + sizeof(dev_state) + 64 + 4096)) return 1;
     const size_t rec_off = (pb + 63) & ~(size_t)63;
     HIPCHK(hipMemcpyAsync(h->stage + rec_off + rb, h->dstate, sizeof(dev_state), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(h->stage + rec_off, d_recs, rb, hipMemcpyDeviceToHost, h->stream));
@@ -1991,11 +1971,47 @@ static int state_and_results_to_stage(gh_handle *h, dev_state *hs, const uint8_t
     return GH_OK;
 }
 
-static void stage_deliver(gh_handle *h, uint8_t *paths_out, size_t n1, gh_path_rec *recs, int launched, int n_done)
+// zeroes n control words of the window from *word on (lt_stale and, behind it, cw_unres; cw_need), on the handle's stream
+static int clear_flags(gh_handle *h, int *word, int n = 1)
 {
-    const size_t rec_off = (n1 * (size_t)launched + 63) & ~(size_t)63;
-    memcpy(paths_out, h->stage, n1 * (size_t)n_done);
-    memcpy(recs, h->stage + rec_off, sizeof(gh_path_rec) * (size_t)n_done);
+    static const int zero[2] = {0, 0};
+    const hipError_t e = hipMemcpyAsync(word, zero, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, h->stream);
+    return e == hipSuccess ? GH_OK : fail(GH_ERR_HIP, "gh_spin failed: %s", hipGetErrorString(e));
+}
+
+// The end of a queue of n paths.  hp: the likelihood sums of every path in one launch (strictly sequential additions, one wavefront per
+// sum).  lt_baked >= 0: the table in step with the last reweight while its path is still allocated (in full when a candidate mask moved).
+// Then the removed mass of every path in one launch, and the state and the results in one wait (*staged: they lie in the pinned buffer)
+static int finish_spin(gh_handle *h, const spin_io &io, int n, bool hp, int lt_baked, dev_state &hs, bool *staged)
+{
+    int rc;
+    *staged = false;
+    if (n <= 0) return read_state(h, &hs);
+    if (hp) {
+        hipLaunchKernelGGL(k_hp, dim3(n, 2), dim3(64), 0, h->stream, (const double *)h->spin_lmsel, io.n1, (const uint8_t *)h->spin_paths, io.n1,
+                           (const double *)h->minfo, h->N, (const dev_state *)h->dstate, h->spin_recs, h->sm);
+        if ((rc = post_launch(h, "k_hp"))) return rc;
+    }
+    if (lt_baked >= 0 && (rc = ensure_lt(h, lt_baked != 0, true, io.plan.flow == GH_FLOW_FUSE))) return rc;
+    if (!io.no_reweight) {
+        hipLaunchKernelGGL(k_reweight_finish_all, dim3(n), dim3(256), 0, h->stream, h->partial, io.plan.stride, h->dstate, h->spin_recs);
+        if ((rc = post_launch(h, "k_reweight_finish_all"))) return rc;
+    }
+    const int sr = state_and_results_to_stage(h, &hs, h->spin_paths, io.n1, h->spin_recs, n);
+    if (sr < 0) return sr;
+    *staged = sr == GH_OK;
+    return *staged ? GH_OK : read_state(h, &hs);
+}
+
+// the n_done complete paths of the `launched` ones to the caller
+static int deliver_results(gh_handle *h, const spin_io &io, const dev_state &hs, int launched, bool staged)
+{
+    const size_t pb = io.n1 * (size_t)hs.n_done, rb = sizeof(gh_path_rec) * (size_t)hs.n_done;
+    if (hs.n_done <= 0) return GH_OK;
+    if (!staged || hs.n_done > launched) return results_to_host(h, io.paths_out, h->spin_paths, pb, io.recs, h->spin_recs, rb);
+    memcpy(io.paths_out, h->stage, pb);
+    memcpy(io.recs, h->stage + ((io.n1 * (size_t)launched + 63) & ~(size_t)63), rb);
+    return GH_OK;
 }
 
 // The spin of lag counts 6 .. 24: segments walked from candidate pools (cwalk.hpp).  The paths are queued a few at a
@@ -2009,25 +2025,23 @@ static int spin_candidate_pools(gh_handle *h, const spin_io &io, dev_state &hs, 
     const int max_paths = io.max_paths;
     const double min_remove = io.min_remove;
     const size_t n1 = io.n1;
-    const int nb = io.nb;
-    uint8_t *d_paths = io.d_paths, *paths_out = io.paths_out;
-    gh_path_rec *d_recs = io.d_recs, *recs = io.recs;
-    hipError_t e = hipSuccess;
+    uint8_t *d_paths = h->spin_paths;
+    gh_path_rec *d_recs = h->spin_recs;
     int rc = GH_OK, first = 0;
     bool cw_gave_up = false;
-    rc = alloc_cw(h);
+    if ((rc = alloc_cw(h))) return rc;
     const cw_geom cg = cw_geometry(h->N, h->L);
     // what follows the kernels of a path: the fused reweight (which also closes the path's record), or only the closing
     auto finish_path = [&](uint8_t *pth, gh_path_rec *rec, int slot, bool chained) -> int {
-        if (!io.no_reweight) return launch_reweight_marg(h, pth, min_remove, 1, rec, slot, true, chained, cg.S);
+        if (!io.no_reweight) {
+            rw_req q;
+            q.path = pth; q.rec = rec; q.ratio = min_remove; q.slot = slot; q.seg = true; q.chained = chained; q.nseg = cg.S;
+            return launch_reweight_marg(h, io.plan, q);
+        }
         hipLaunchKernelGGL(k_seg_fin, dim3(1), dim3(256), 0, h->stream, seg_make_params(h, 0, 0, nullptr, nullptr), rec, min_remove, cg.S);
         return post_launch(h, "k_seg_fin");
     };
-    const int zero2[2] = {0, 0};
-    if (rc == GH_OK) {
-        e = hipMemcpyAsync(&h->dstate->lt_stale, zero2, sizeof zero2, hipMemcpyHostToDevice, h->stream);      // lt_stale, cw_unres
-        if (e != hipSuccess) rc = fail(GH_ERR_HIP, "gh_spin failed: %s", hipGetErrorString(e));
-    }
+    if ((rc = clear_flags(h, &h->dstate->lt_stale, 2))) return rc;      // lt_stale, cw_unres
     // which layout did k_lt choose for this tensor?  (ranks when every position has at most four candidates, else symbols:
     // the walker's instantiation, the bits per pick and what a pool entry means follow from it)
     auto look_at_layout = [&](int ranked) {
@@ -2054,10 +2068,10 @@ static int spin_candidate_pools(gh_handle *h, const spin_io &io, dev_state &hs, 
             }
         }
     };
-    if (rc == GH_OK) rc = ensure_lt(h);
-    if (rc == GH_OK) {
+    {
         dev_state look;
-        if ((rc = read_state(h, &look)) == GH_OK) look_at_layout(look.ranked);
+        if ((rc = ensure_lt(h)) || (rc = read_state(h, &look))) return rc;
+        look_at_layout(look.ranked);
     }
     int done = 0;
     int CHUNK = 8, clean = 0;        // paths queued between two looks at the device state: grows while every chain closes
@@ -2066,10 +2080,8 @@ static int spin_candidate_pools(gh_handle *h, const spin_io &io, dev_state &hs, 
             // a position with five candidates: the rest of the spin goes the serial walkers' way (the loop below)
             cw_gave_up = true;
             first = done;
-            if (done < max_paths) {
-                e = hipMemset2DAsync(h->spin_lmsel + n1 * done, n1 * sizeof(double), 0, sizeof(double), (size_t)(max_paths - done), h->stream);
-                if (e != hipSuccess) rc = fail(GH_ERR_HIP, "gh_spin failed: %s", hipGetErrorString(e));
-            }
+            if (hipMemset2DAsync(h->spin_lmsel + n1 * done, n1 * sizeof(double), 0, sizeof(double), (size_t)(max_paths - done), h->stream) != hipSuccess)
+                rc = fail(GH_ERR_HIP, "gh_spin failed: hipMemset2DAsync");
             break;
         }
         if (!h->cw_ready) {
@@ -2079,11 +2091,11 @@ static int spin_candidate_pools(gh_handle *h, const spin_io &io, dev_state &hs, 
             h->cw_stamp++;
             if ((rc = ensure_lt(h))) break;
             uint8_t *pth = d_paths + n1 * done;
-            cw_params P = cw_make_params(h, pth, h->spin_lmsel + n1 * done);
+            cw_params P = cw_make_params(h, pth, h->spin_lmsel + n1 * done, io.no_reweight);
             hipLaunchKernelGGL(k_cguess, dim3((unsigned)((h->N + 256) / 256)), dim3(256), 0, h->stream, P, pth);
             hipLaunchKernelGGL(k_cseed, dim3((cg.S + 255) / 256), dim3(256), 0, h->stream, P, (const uint8_t *)pth, 0);
             if ((rc = post_launch(h, "k_cguess/k_cseed"))) break;
-            if ((rc = launch_cw_path(h, pth, h->spin_lmsel + n1 * done, CW_BOOT_ROUNDS, 0))) break;
+            if ((rc = launch_cw_path(h, pth, h->spin_lmsel + n1 * done, CW_BOOT_ROUNDS, 0, io.no_reweight))) break;
             if ((rc = finish_path(pth, d_recs + done, done, false))) break;
             h->cw_stat[2] += CW_BOOT_ROUNDS;
             h->cw_ready = true;
@@ -2096,7 +2108,7 @@ static int spin_candidate_pools(gh_handle *h, const spin_io &io, dev_state &hs, 
             for (int s = done; s < upto && rc == GH_OK; s++) {
                 h->cw_stamp++;
                 if (!inc && s > done && (rc = ensure_lt(h))) break;
-                if ((rc = launch_cw_path(h, d_paths + n1 * s, h->spin_lmsel + n1 * s, h->cw_rounds, (inc && s > done) ? 1 : 0))) break;
+                if ((rc = launch_cw_path(h, d_paths + n1 * s, h->spin_lmsel + n1 * s, h->cw_rounds, (inc && s > done) ? 1 : 0, io.no_reweight))) break;
                 rc = finish_path(d_paths + n1 * s, d_recs + s, s, s > done);
                 h->cw_stat[2] += h->cw_rounds;
             }
@@ -2116,15 +2128,10 @@ static int spin_candidate_pools(gh_handle *h, const spin_io &io, dev_state &hs, 
             // idle rounds cost three launches each: one fewer when, three looks in a row, no path needed as many as are queued
             if (hs.cw_need > 0 && hs.cw_need < h->cw_rounds) { if (++clean >= 3) { h->cw_rounds--; clean = 0; } }
             else clean = 0;
-            if (hs.cw_need > 0) {
-                const int zero = 0;
-                e = hipMemcpyAsync(&h->dstate->cw_need, &zero, sizeof zero, hipMemcpyHostToDevice, h->stream);
-                if (e != hipSuccess) { rc = fail(GH_ERR_HIP, "gh_spin failed: %s", hipGetErrorString(e)); break; }
-            }
+            if (hs.cw_need > 0 && (rc = clear_flags(h, &h->dstate->cw_need))) break;
         } else { CHUNK = 8; clean = 0; }
         if (hs.lt_stale || hs.cw_unres) {
-            e = hipMemcpyAsync(&h->dstate->lt_stale, zero2, sizeof zero2, hipMemcpyHostToDevice, h->stream);
-            if (e != hipSuccess) { rc = fail(GH_ERR_HIP, "gh_spin failed: %s", hipGetErrorString(e)); break; }
+            if ((rc = clear_flags(h, &h->dstate->lt_stale, 2))) break;
             h->spin_requeues++;
             h->cw_stat[3]++;
             // a moved candidate mask or a window for the serial walkers: the next ensure_lt rebuilds the table in
@@ -2150,22 +2157,19 @@ static int spin_candidate_pools(gh_handle *h, const spin_io &io, dev_state &hs, 
                     const int more = h->L > 16 ? 48 : 12;
                     const int tries = h->L > 16 ? (cg.S + 16) / more + 1 : 1;
                     for (int a = 0; a < tries && !closed; a++) {
-                        if ((rc = launch_cw_path(h, d_paths + n1 * done, h->spin_lmsel + n1 * done, more, 0, true))) break;
+                        if ((rc = launch_cw_path(h, d_paths + n1 * done, h->spin_lmsel + n1 * done, more, 0, io.no_reweight, true))) break;
                         if ((rc = finish_path(d_paths + n1 * done, d_recs + done, done, false))) break;
                         h->cw_stat[2] += more;
                         if ((rc = read_state(h, &hs))) break;
                         closed = !hs.cw_unres && hs.n_done > done;
-                        if (hs.cw_unres) {
-                            e = hipMemcpyAsync(&h->dstate->lt_stale, zero2, sizeof zero2, hipMemcpyHostToDevice, h->stream);
-                            if (e != hipSuccess) { rc = fail(GH_ERR_HIP, "gh_spin failed: %s", hipGetErrorString(e)); break; }
-                        }
+                        if (hs.cw_unres && (rc = clear_flags(h, &h->dstate->lt_stale, 2))) break;
                         if (hs.stop) break;
                     }
                     if (rc != GH_OK) break;
                 }
                 if (!closed) {
                     h->cw_stamp++;
-                    if ((rc = cw_serial_path(h, d_paths + n1 * done, d_recs + done, h->spin_lmsel + n1 * done, min_remove, done, 1, !io.no_reweight))) break;
+                    if ((rc = cw_serial_path(h, io, d_paths + n1 * done, d_recs + done, h->spin_lmsel + n1 * done, done, 1))) break;
                     if ((rc = read_state(h, &hs))) break;
                 }
                 done = hs.n_done;
@@ -2180,16 +2184,93 @@ static int spin_candidate_pools(gh_handle *h, const spin_io &io, dev_state &hs, 
         h->dirty_lt = true;
     }
     if (rc == GH_OK && done > 0 && !cw_gave_up) {
-        hipLaunchKernelGGL(k_hp, dim3(done, 2), dim3(64), 0, h->stream, (const double *)h->spin_lmsel, n1, (const uint8_t *)d_paths, n1,
-                           (const double *)h->minfo, h->N, (const dev_state *)h->dstate, d_recs, h->sm);
-        if (!io.no_reweight) hipLaunchKernelGGL(k_reweight_finish_all, dim3(done), dim3(256), 0, h->stream, h->partial, nb, h->dstate, d_recs);
-        rc = post_launch(h, "k_hp/k_reweight_finish_all");
-        if (rc == GH_OK && (rc = read_state(h, &hs)) == GH_OK && hs.n_done > 0)
-            rc = results_to_host(h, paths_out, d_paths, n1 * hs.n_done, recs, d_recs, sizeof(gh_path_rec) * hs.n_done);
+        bool staged;
+        if ((rc = finish_spin(h, io, done, true, -1, hs, &staged)) == GH_OK) rc = deliver_results(h, io, hs, done, staged);
     }
     *first_out = first;
     *gave_up = cw_gave_up;
     return rc;
+}
+
+// ---- which kernels run for every path of a spin: chosen once, as a value (DESIGN.md section 4.1 has the table) ----------------
+static int sw(int v, int def) { return v < 0 ? def : v; }      // a switch of gh_spin_plan_in: -1 = unset
+
+// Pure: no HIP call, no handle.  in.ranked < 0 and a choice that depends on the table's layout: need_layout, nothing else.
+static spin_plan plan_spin(const gh_spin_plan_in &in)
+{
+    spin_plan p{};
+    const int N = in.n_snps, W = in.band, L = in.L, wm = in.walk_mode;
+    const bool col = in.cond_mode == GH_COND_C || in.cond_mode == GH_COND_E;
+    const int lanes = rw_lanes_of(W, L, col, sw(in.rw_lp16, 1) != 0, sw(in.rw_tband, 1) != 0);
+    bool seg = seg_ok(wm, L);
+    if (!seg && wm == WM_SEG && L == SEG_MAX_L_NARROW && sw(in.seg6, 1) != 0) {
+        // 4^6 states can still be enumerated -- 5^6 cannot: the layout k_lt chose decides (narrow stays narrow: candidates only disappear)
+        if (in.ranked < 0) { p.need_layout = 1; return p; }
+        p.seg6 = seg = in.ranked != 0;
+    }
+    p.rw_lanes = (seg || cw_ok(wm, L)) ? lanes : 8;
+    p.stride = rw_blocks_of(N, p.rw_lanes);                     // the blocks of the widest reweight kernel this spin may launch
+    if (!seg) {
+        p.flow = (cw_ok(wm, L) && !in.pools_off) ? GH_FLOW_POOLS : GH_FLOW_SERIAL;
+        p.S = p.flow == GH_FLOW_POOLS ? cw_geometry(N, L).S : 0;
+        return p;
+    }
+    p.S = seg_S(N, L);
+    // three launches, no k_emit: where the group maps fit k_rw's LDS and the band the halo it resolves; bit-identical but measured
+    // slower than four (docs/HISTORY.md, H), so opt-in: GH_FUSE=1 (large windows) or 2 (every window the maps fit; the tests)
+    const int fuse = sw(in.fuse, 0);
+    if (in.need_rinfo && W <= RW_FUSE_HALO && lanes == 8 && fuse >= 1) {
+        if (in.ranked < 0) { p = spin_plan{}; p.need_layout = 1; return p; }
+        const int R = in.ranked ? 4 : 5;
+        const size_t lds = rw_fuse_lds_bytes(N, L, R, 256 / lanes, W);
+        const bool small_r = emit_small_lds_bytes(N, L, R) <= 64 * 1024 && sw(in.emit_small, 1) != 0;
+        // (small windows -- by the table's own radix -- keep k_emit_small: three launches too)
+        if ((!small_r || fuse == 2) && seg_radix_ok(R, L) && lds <= 64 * 1024) { p.flow = GH_FLOW_FUSE; p.lds = (int64_t)lds; return p; }
+    }
+    p.flow = GH_FLOW_SEG;
+    p.emit_small = emit_small_ok(N, L, in.emit_small);
+    p.mixed = mixed_ok(sw(in.mixed, 1) != 0, false, L, wm, in.offer_zero);
+    // k_rwseg: the reweight of a path rides in the k_seg launch of the next one.  Lane groups of 8, at most 128 positions per workgroup
+    // with the halo, and its LDS must fit (the column conditionals stage the band blocks of all those positions)
+    if (!in.lt_full && lanes == 8 && sw(in.rwseg, 1) != 0 && (!p.emit_small || sw(in.rwseg_small, 1) != 0)) {
+        const int longest = (int)max_cls(L, [&](int R) { return (size_t)seg_geometry(N, L, R).seglen; });
+        const size_t lds = rws_patch_off(N, W, L, col, in.storage == GH_STORAGE_F64 ? 8 : 4) + sizeof(seg_patch);
+        if (longest + L + 1 <= SEG_THREADS / 8 && lds <= RWS_LDS_MAX) {
+            p.flow = GH_FLOW_RWSEG; p.lds = (int64_t)lds;
+            if (p.S > p.stride) p.stride = p.S;                 // k_rwseg leaves one partial sum per segment
+        }
+    }
+    return p;
+}
+
+// what the choice depends on for this handle; the layout not looked at
+static gh_spin_plan_in plan_inputs(const gh_handle *h)
+{
+    gh_spin_plan_in in{};
+    in.n_snps = h->N; in.band = h->W; in.L = h->L; in.storage = h->cfg.storage; in.cond_mode = h->cfg.cond_mode;
+    in.marginal_term = h->cfg.marginal_term; in.offer_zero = h->cfg.offer_zero; in.ranked = -1;
+    in.walk_mode = h->wmode; in.lt_full = h->lt_full; in.need_rinfo = h->need_rinfo; in.pools_off = h->cw_off;
+    in.rwseg = env_int("GH_RWSEG", -1); in.rwseg_small = env_int("GH_RWSEG_SMALL", -1); in.emit_small = env_int("GH_EMIT_SMALL", -1);
+    in.fuse = env_int("GH_FUSE", -1); in.seg6 = env_int("GH_SEG6", -1);
+    in.mixed = mixed_on(); in.rw_lp16 = rw_lp16_on(); in.rw_tband = rw_tband_on();      // (per process)
+    return in;
+}
+
+extern "C" int gh_debug_spin_plan(const gh_spin_plan_in *in, gh_spin_plan *out)
+{
+    if (!in || !out) return fail(GH_ERR_ARG, "null argument");
+    if (in->n_snps < 1 || in->band < 1 || in->L < 1 || (in->storage != GH_STORAGE_F32 && in->storage != GH_STORAGE_F64) ||
+        in->cond_mode < GH_COND_A || in->cond_mode > GH_COND_E || in->walk_mode < WM_SEG || in->walk_mode > WM_SRC || in->ranked < -1 || in->ranked > 1)
+        return fail(GH_ERR_ARG, "spin plan: n_snps >= 1, band >= 1, L >= 1, a storage, a conditional, a walk mode, ranked in -1..1");
+    *out = plan_spin(*in);
+    return GH_OK;
+}
+
+extern "C" int gh_debug_last_spin_plan(gh_t *h, gh_spin_plan *out)
+{
+    if (!h || !out) return fail(GH_ERR_ARG, "null argument");
+    *out = h->last_plan;
+    return GH_OK;
 }
 
 extern "C" int gh_spin(gh_t *h, int max_paths, double min_remove, uint8_t *paths_out, gh_path_rec *recs,
@@ -2202,162 +2283,78 @@ extern "C" int gh_spin(gh_t *h, int max_paths, double min_remove, uint8_t *paths
     if (max_paths == 0) return GH_OK;
     int rc;
     if (!h->have_orig && (rc = gh_snapshot_original(h))) return rc;
-    const size_t n1 = (size_t)h->N + 1;
     if ((rc = ensure_spin_buffers(h, max_paths))) return rc;
-    uint8_t *d_paths = h->spin_paths;
-    gh_path_rec *d_recs = h->spin_recs;
-    hipError_t e = hipSuccess;
-    rc = GH_OK;
-    bool seg = seg_ok(h->wmode, h->L);
-    h->seg6 = false;
-    if (rc == GH_OK && !seg && h->wmode == WM_SEG && h->L == SEG_MAX_L_NARROW && !env_off("GH_SEG6")) {
-        // 4^6 states can still be enumerated -- 5^6 cannot: look at the layout k_lt chose for this tensor (a window that is
-        // narrow stays narrow: candidates only ever disappear)
+    spin_io io{};
+    io.max_paths = max_paths; io.min_remove = min_remove; io.n1 = (size_t)h->N + 1; io.paths_out = paths_out; io.recs = recs;
+    gh_spin_plan_in in = plan_inputs(h);
+    io.plan = plan_spin(in);
+    if (io.plan.need_layout) {
+        // which layout did k_lt choose for this tensor?  One look per spin, only where the choice depends on it
         dev_state look;
-        if ((rc = ensure_lt(h)) == GH_OK && (rc = read_state(h, &look)) == GH_OK && look.ranked) { seg = true; h->seg6 = true; }
+        if ((rc = ensure_lt(h)) || (rc = read_state(h, &look))) return rc;
+        in.ranked = look.ranked ? 1 : 0;
+        io.plan = plan_spin(in);
     }
-    // Spins over the enumerated states run without k_emit where the group maps fit k_rw's LDS beside everything else
-    // (1024 states: 32 KB; the five-symbol radix from 5^5 states on, and 4^6, keep k_emit) and the band is not wider than
-    // the halo k_rw resolves: which radix applies is the table's layout, decided on the device -- one look per spin.
-    h->fuse = false;
-    // MEASURED (C3, MI355X): three launches are bit-identical but NOT faster than four -- k_emit and its
-    // boundary (6.8 us) go, the prologue k_rw needs instead (group maps to LDS, the chain, one more round trip) costs 6.5 us,
-    // and carrying the minima through k_seg / k_scan another 2.9 us: 40.8 against 38.7 us per path.  So it is opt-in:
-    // GH_FUSE=1 (large windows) or 2 (every window the maps fit; the tests).
-    if (rc == GH_OK && seg && h->need_rinfo && h->W <= RW_FUSE_HALO && rw_lanes(h) == 8 && env_int("GH_FUSE", 0) >= 1) {
-        dev_state look;
-        if ((rc = ensure_lt(h)) == GH_OK && (rc = read_state(h, &look)) == GH_OK) {
-            const int R = look.ranked ? 4 : 5;
-            const int ppb = 256 / rw_lanes(h);
-            // (windows whose segment maps all fit one workgroup's LDS keep k_emit_small: three launches as well, and a lighter k_rw)
-            const bool small = emit_small_lds_bytes(h->N, h->L, R) <= 64 * 1024 && !env_off("GH_EMIT_SMALL");
-            const bool force = env_int("GH_FUSE", 0) == 2;      // (tests: fused whatever the size)
-            if ((!small || force) && seg_radix_ok(R, h->L) && rw_fuse_lds_bytes(h->N, h->L, R, ppb, h->W) <= 64 * 1024 && (rc = alloc_seg(h)) == GH_OK) {
-                h->fuse = true;
-                h->fuse_lds = rw_fuse_lds_bytes(h->N, h->L, R, ppb, h->W);
-                // (this spin walks the enumerated states: whatever k_classify found before the flow was chosen does not apply)
-                if (hipMemsetAsync(&h->dstate->maxstates, 0, sizeof(int), h->stream) != hipSuccess) rc = fail(GH_ERR_HIP, "gh_spin failed: hipMemsetAsync");
-            }
-        }
+    const spin_plan &plan = h->last_plan = io.plan;
+    const bool rws = plan.flow == GH_FLOW_RWSEG, fused = plan.flow == GH_FLOW_FUSE, seg = rws || fused || plan.flow == GH_FLOW_SEG;
+    if ((rws || fused) && (rc = alloc_seg(h))) return rc;
+    // (the three-launch flow walks the enumerated states: whatever k_classify found before the flow was chosen does not apply)
+    if (fused) HIPCHK(hipMemsetAsync(&h->dstate->maxstates, 0, sizeof(int), h->stream));
+    const size_t halo = rws ? (size_t)plan.S * h->L * NSYM * h->W * NSYM * esize(h) : 0;
+    if (halo > h->seg_halo_bytes) {
+        HIPCHK(hipStreamSynchronize(h->stream));
+        hipFree(h->seg_halo); h->seg_halo = nullptr; h->seg_halo_bytes = 0;
+        if (hipMalloc(&h->seg_halo, halo) != hipSuccess) return fail(GH_ERR_NOMEM, "hipMalloc failed");
+        h->seg_halo_bytes = halo;
     }
-    // k_rwseg (segwalk.hpp): the reweight of a path rides in the k_seg launch of the next one.  Lane groups of 8 (bands up to 8),
-    // at most 128 positions per workgroup with the halo; behind it k_scan + k_emit, or k_emit_small alone in small windows.
-    h->rws = false;
-    int rws_S = 0;
-    if (rc == GH_OK && seg && !h->fuse && !h->lt_full && rw_lanes(h) == 8 && !env_off("GH_RWSEG")) {
-        const bool five = seg_radix_ok(5, h->L);
-        const seg_geom g4 = seg_geometry(h->N, h->L, 4), g5 = five ? seg_geometry(h->N, h->L, 5) : g4;
-        const bool small = (five ? max2(emit_small_lds_bytes(h->N, h->L, 4), emit_small_lds_bytes(h->N, h->L, 5)) : emit_small_lds_bytes(h->N, h->L, 4)) <= 64 * 1024 &&
-                           !env_off("GH_EMIT_SMALL");
-        const int longest = g4.seglen > g5.seglen ? g4.seglen : g5.seglen;
-        // (... and the kernel's LDS must fit: the column conditionals stage the band blocks of all those positions -- long
-        // segments of a wide band in binary64 do not)
-        // (small windows -- k_emit_small behind k_rwseg, two launches per path -- unless GH_RWSEG_SMALL=0)
-        const bool small_ok = !env_off("GH_RWSEG_SMALL");
-        if ((!small || small_ok) && longest + h->L + 1 <= SEG_THREADS / 8 && rws_patch_off(h, h->L) + sizeof(seg_patch) <= RWS_LDS_MAX &&
-            (rc = alloc_seg(h)) == GH_OK) {
-            rws_S = g4.S > g5.S ? g4.S : g5.S;
-            const size_t need = (size_t)rws_S * h->L * NSYM * h->W * NSYM * esize(h);
-            if (need > h->seg_halo_bytes) {
-                // (no early return from here on: the cleanup at the end of this function resets fuse / rws / the stride)
-                if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) rc = fail(GH_ERR_HIP, "gh_spin failed: %s", hipGetErrorString(e));
-                else {
-                    hipFree(h->seg_halo); h->seg_halo = nullptr; h->seg_halo_bytes = 0;
-                    if (hipMalloc(&h->seg_halo, need) != hipSuccess) rc = fail(GH_ERR_NOMEM, "hipMalloc failed");
-                    else h->seg_halo_bytes = need;
-                }
-            }
-            h->rws = rc == GH_OK;
-        }
-    }
-    int nb = rw_blocks(h, seg || cw_ok(h->wmode, h->L));       // (the widest reweight kernel this spin may launch)
-    if (h->rws && rws_S > nb) nb = rws_S;                       // ... k_rwseg leaves one partial sum per segment
-    h->spin_partial_stride = nb;
-    if (rc == GH_OK) rc = ensure_partial(h, nb, max_paths > h->spin_cap ? max_paths : h->spin_cap);       // L only changes through gh_set_L / gh_fill, never inside a spin
+    // L only changes through gh_set_L / gh_fill, never inside a spin
+    if ((rc = ensure_partial(h, plan.stride, max_paths > h->spin_cap ? max_paths : h->spin_cap))) return rc;
     // (k_rwseg: every slot is summed over the whole stride: what a kernel with fewer workgroups leaves untouched must read 0)
-    if (rc == GH_OK) rc = reset_spin_state(h, h->rws ? h->partial : nullptr, h->rws ? (size_t)nb * max_paths : 0);
-    // Segment-parallel walks with a conditional table that the fused reweight keeps current (conditional A/B, no marginal
-    // term): no k_lt between two paths.  Its only job there is to notice that a candidate mask moved (a count reached
-    // zero; rare) and rebuild the table; instead the next k_seg sees the flag k_marg left, marks the table stale and the
-    // rest of the queue does nothing.  The host then rebuilds and queues the remaining paths again.
+    if ((rc = reset_spin_state(h, rws ? h->partial : nullptr, rws ? (size_t)plan.stride * max_paths : 0))) return rc;
+    // no k_lt between two paths over the enumerated states: the reweight keeps the table current, and where a candidate mask moved
+    // (rare) the next k_seg marks the table stale and the rest of the queue idles; the host rebuilds and queues the rest again
     const bool optimistic = seg && !h->lt_full;
     dev_state hs;
     memset(&hs, 0, sizeof hs);
     int first = 0;
-    h->spin_requeues = 0;
-    // lag counts 6 .. 24: segments walked from candidate pools (spin_candidate_pools above)
-    const bool cw = rc == GH_OK && !seg && cw_ok(h->wmode, h->L) && !h->cw_off;
     bool cw_gave_up = false;
-    if (cw) {
-        spin_io io;
-        io.max_paths = max_paths; io.min_remove = min_remove; io.n1 = n1; io.nb = nb;
-        io.d_paths = d_paths; io.d_recs = d_recs; io.paths_out = paths_out; io.recs = recs; io.no_reweight = false;
-        rc = spin_candidate_pools(h, io, hs, &first, &cw_gave_up);
-    }
-    while ((!cw || cw_gave_up) && rc == GH_OK) {
+    h->spin_requeues = 0;
+    if (plan.flow == GH_FLOW_POOLS && (rc = spin_candidate_pools(h, io, hs, &first, &cw_gave_up))) return rc;
+    // (the pools hand paths `first` .. to the serial walkers when the window turns out to have a position with five candidates)
+    while (plan.flow != GH_FLOW_POOLS || cw_gave_up) {
         int launched = first;
-        for (int s = first; s < max_paths && rc == GH_OK; s++) {
-            if (!optimistic || s == first) { if ((rc = ensure_lt(h, !seg))) break; }
+        for (int s = first; s < max_paths; s++) {
+            if ((!optimistic || s == first) && (rc = ensure_lt(h, !seg, true, fused))) return rc;
             const int cmk = !(optimistic && s > first) ? 0 : (s == h->force_stale_at && h->spin_requeues == 0 ? 2 : 1);
-            if (h->rws) {
-                // path s is walked by the launch that reweights path s - 1; the last path's reweight is a plain k_rw
-                if (s == first) rc = launch_walk(h, d_paths + n1 * s, d_recs + s, min_remove, 1, h->spin_lmsel + n1 * s, cmk);
-                else rc = launch_rwseg(h, d_paths + n1 * (s - 1), d_recs + (s - 1), s - 1, min_remove, d_paths + n1 * s, h->spin_lmsel + n1 * s, cmk);
-                if (rc == GH_OK && s == max_paths - 1)
-                    rc = launch_reweight_marg(h, d_paths + n1 * s, min_remove, 1, d_recs + s, s, true, s > first, 0, h->spin_lmsel + n1 * s);
-                if (rc) break;
-                launched = s + 1;
-                continue;
+            uint8_t *pth = h->spin_paths + io.n1 * s;
+            double *lmsel = h->spin_lmsel + io.n1 * s;
+            // k_rwseg: path s is walked by the launch that reweights path s - 1; the last path's reweight is a plain k_rw
+            if (rws && s > first) rc = launch_rwseg(h, plan, pth - io.n1, h->spin_recs + (s - 1), s - 1, min_remove, pth, lmsel, cmk);
+            else rc = launch_walk(h, plan, pth, h->spin_recs + s, min_remove, 1, lmsel, cmk);
+            if (rc) return rc;
+            if (!rws || s == max_paths - 1) {
+                rw_req q;
+                q.path = pth; q.rec = h->spin_recs + s; q.ratio = seg ? min_remove : 0.0; q.slot = s; q.seg = seg;
+                q.chained = optimistic && s > first; q.lmsel = lmsel;
+                if ((rc = launch_reweight_marg(h, plan, q))) return rc;
             }
-            if ((rc = launch_walk(h, d_paths + n1 * s, d_recs + s, min_remove, 1, h->spin_lmsel + n1 * s, cmk))) break;
-            if ((rc = launch_reweight_marg(h, d_paths + n1 * s, seg ? min_remove : 0.0, 1, d_recs + s, s, seg, optimistic && s > first, 0,
-                                           h->spin_lmsel + n1 * s))) break;
             launched = s + 1;
         }
-        // the likelihood sums of every path in one launch (strictly sequential additions, one wavefront per sum)
-        if (rc == GH_OK && launched > 0 && (seg || cw_gave_up)) {
-            hipLaunchKernelGGL(k_hp, dim3(launched, 2), dim3(64), 0, h->stream, (const double *)h->spin_lmsel, n1, (const uint8_t *)d_paths, n1,
-                               (const double *)h->minfo, h->N, (const dev_state *)h->dstate, d_recs, h->sm);
-            rc = post_launch(h, "k_hp");
-        }
-        // bring the table in step with the last reweight while its path is still allocated (the next call would
-        // otherwise refresh it from a freed buffer); rebuilds it in full when a candidate mask moved
-        if (rc == GH_OK && launched > 0) rc = ensure_lt(h, !seg);
-        // the removed mass of every path in one launch (it is only ever read by the host)
-        if (rc == GH_OK && launched > 0) {
-            hipLaunchKernelGGL(k_reweight_finish_all, dim3(launched), dim3(256), 0, h->stream, h->partial, nb, h->dstate, d_recs);
-            rc = post_launch(h, "k_reweight_finish_all");
-        }
-        if (rc != GH_OK) break;
-        // state and results in one wait (the results of a queue that has to be taken up again are fetched in vain: rare)
-        bool staged = false;
-        if (launched > 0) {
-            const int sr = state_and_results_to_stage(h, &hs, d_paths, n1, d_recs, launched);
-            if (sr < 0) { rc = sr; break; }
-            staged = sr == GH_OK;
-        }
-        if (!staged && (rc = read_state(h, &hs))) break;
+        bool staged;
+        if ((rc = finish_spin(h, io, launched, seg || cw_gave_up, seg ? 0 : 1, hs, &staged))) return rc;
         if (getenv("GH_PRINT_STATE"))
             fprintf(stderr, "gh_spin: stop %d hole_at %d n_done %d first_hole %d cur_hole %d lt_stale %d cm_same %d narrow %d ranked %d\n", hs.stop, hs.hole_at,
                     hs.n_done, hs.first_hole, hs.cur_hole, hs.lt_stale, hs.cm_same, hs.narrow, hs.ranked);
-        if (e == hipSuccess && optimistic && hs.lt_stale && !hs.stop && hs.n_done < max_paths) {
-            // paths 0 .. n_done-1 are complete; the table has just been rebuilt by the ensure_lt above
-            const int zero = 0;
-            e = hipMemcpyAsync(&h->dstate->lt_stale, &zero, sizeof zero, hipMemcpyHostToDevice, h->stream);
-            if (e == hipSuccess) { first = hs.n_done; h->spin_requeues++; continue; }
+        if (optimistic && hs.lt_stale && !hs.stop && hs.n_done < max_paths) {
+            // paths 0 .. n_done-1 are complete; the table has just been rebuilt (finish_spin): queue the rest again
+            if ((rc = clear_flags(h, &h->dstate->lt_stale))) return rc;
+            first = hs.n_done;
+            h->spin_requeues++;
+            continue;
         }
-        if (e != hipSuccess) rc = fail(GH_ERR_HIP, "gh_spin failed: %s", hipGetErrorString(e));
-        else if (hs.n_done > 0) {
-            if (staged && hs.n_done <= launched) stage_deliver(h, paths_out, n1, recs, launched, hs.n_done);
-            else rc = results_to_host(h, paths_out, d_paths, n1 * hs.n_done, recs, d_recs, sizeof(gh_path_rec) * hs.n_done);
-        }
+        if ((rc = deliver_results(h, io, hs, launched, staged))) return rc;
         break;
     }
-    h->spin_partial_stride = 0;
-    h->seg6 = false;
-    h->fuse = false;
-    h->rws = false;
-    if (rc) return rc;
     *n_out = hs.n_done;
     *hole_at = hs.stop ? hs.hole_at : 0;
     return GH_OK;

@@ -515,6 +515,14 @@ class Hansel:
         check(self._lib.gh_debug_walk_clock(self._h, out))
         return int(out[0]), int(out[1]), int(out[2]), int(out[3])
 
+    def spin_plan(self):
+        """Which kernels the last spin() ran for every path (gh_spin_plan of include/gretel_hip.h as a dict: flow, emit_small, seg6,
+        stride, rw_lanes, S, mixed, lds); flow "none" before the first spin."""
+        self._ensure()
+        out = _lib.gh_spin_plan()
+        check(self._lib.gh_debug_last_spin_plan(self._h, C.byref(out)))
+        return out.as_dict()
+
     def sync(self):
         if self._h is not None:
             check(self._lib.gh_sync(self._h))

@@ -358,6 +358,39 @@ int gh_debug_segment_stamps(gh_t *h, double *out, int n_workgroups);
  * per segment, out[2] = targets per LDS chunk of the walker, out[3] = bytes of dynamic LDS it is launched with, out[4] = 1 if a state
  * is a packed 64-bit word (k_cwalk), 0 if bytes next to a hash (k_cwalkg), out[5] = threads per workgroup */
 int gh_debug_pool_geometry(int32_t n_snps, int32_t L, int32_t five, int64_t out[6]);
+/* Which kernels run for every path of a gh_spin is chosen once per spin, as a value.  What the choice depends on: */
+typedef struct gh_spin_plan_in {
+    int32_t n_snps, band, L, storage, cond_mode, marginal_term, offer_zero;   /* as gh_config and gh_set_L */
+    int32_t walk_mode;      /* GH_WALK at creation: 0 seg (default), 1 spec, 2 spec1, 3 src */
+    int32_t lt_full;        /* GH_LT_FULL at creation */
+    int32_t need_rinfo;     /* marginal term, or GH_FUSE >= 1 at creation */
+    int32_t pools_off;      /* the window has shown a position the candidate pools cannot take */
+    int32_t ranked;         /* the conditional table's layout: 1 over candidate ranks, 0 over the symbols, -1 not looked at yet */
+    int32_t rwseg, rwseg_small, emit_small, fuse, seg6, mixed;   /* GH_RWSEG, GH_RWSEG_SMALL, GH_EMIT_SMALL, GH_FUSE, GH_SEG6, GH_MIXED: the value, -1 = unset */
+    int32_t rw_lp16, rw_tband;                                   /* GH_RW_LP16, GH_RW_TBAND (per process): the value, -1 = unset */
+} gh_spin_plan_in;
+/* ... and the choice.  All zero: outside a spin (a lone gh_generate_path / gh_reweight_path) */
+enum { GH_FLOW_NONE = 0,
+       GH_FLOW_SERIAL = 1,   /* a serial walker + k_marg<T,true> per path */
+       GH_FLOW_SEG = 2,      /* the enumerated states: k_seg, k_scan + k_emit (or k_emit_small alone), k_rw */
+       GH_FLOW_RWSEG = 3,    /* ... the reweight of a path inside the k_seg launch of the next: k_rwseg, k_scan + k_emit (or k_emit_small) */
+       GH_FLOW_FUSE = 4,     /* ... opt-in (GH_FUSE): k_seg, k_scan, and a k_rw that chains the maps itself */
+       GH_FLOW_POOLS = 5 };  /* candidate pools (L >= 6) */
+typedef struct gh_spin_plan {
+    int32_t flow;           /* GH_FLOW_* */
+    int32_t emit_small;     /* every segment map fits one workgroup's LDS: k_emit_small instead of k_scan + k_emit */
+    int32_t seg6;           /* L = 6 over a ranked table: the enumerated states (4^6), not pools */
+    int32_t stride;         /* doubles between two paths' partial sums of the removed mass */
+    int32_t rw_lanes;       /* lanes per position of the reweight kernel the stride is sized for */
+    int32_t S;              /* segments the spin sizes for (0: serial) */
+    int32_t mixed;          /* the table builds of this spin classify the window for the mixed-radix states (k_classify) */
+    int32_t need_layout;    /* the choice depends on `ranked` and the caller has not looked (ranked = -1): look, and plan again */
+    int64_t lds;            /* dynamic LDS of the flow's largest launch: k_rwseg's patch offset + the patch, or the fused k_rw's prologue (0 otherwise) */
+} gh_spin_plan;
+/* the choice for a window described by *in; no handle, no GPU (tests/test_spin_plan_host.py) */
+int gh_debug_spin_plan(const gh_spin_plan_in *in, gh_spin_plan *out);
+/* the plan the last gh_spin on this handle ran with (all zero: none yet) */
+int gh_debug_last_spin_plan(gh_t *h, gh_spin_plan *out);
 /* algorithmic bytes of the last launch of each kernel */
 int gh_profile_bytes(gh_t *h, int kernel, double *bytes_per_launch);
 

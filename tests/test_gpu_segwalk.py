@@ -150,10 +150,13 @@ def test_three_launches_per_path(L, wide, kw, monkeypatch):
     res, ref = h.spin(9), o.spin(9)
     same(res, ref)
     assert h.walk_clock()[3] == 3
+    assert h.spin_plan()["flow"] == ("rwseg" if wide and L == 5 else "fuse")
+    assert h.profile_get()["reweight"]["launches"] == (1 if wide and L == 5 else 9)
     assert np.array_equal(h.export_band(), o.export_band())
     monkeypatch.setenv("GH_FUSE", "0")
     h2, _ = make_pair(t, L=L, **kw)
     same(h2.spin(9), ref)
+    assert h2.spin_plan()["flow"] == "rwseg"
     assert np.array_equal(h2.export_band(), o.export_band())
 
 
