@@ -323,6 +323,7 @@ def io_lib():
         L.gio_count_coverage.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p]
         L.gio_release_buffers.argtypes = []
         L.gio_release_buffers.restype = None
+        L.gio_debug_depth_shown.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32]
         _io = L
     return _io
 
@@ -351,6 +352,16 @@ def native_ref_len(bam_path, contig):
     if L.gio_ref_len(bam_path.encode(), contig.encode(), C.byref(out)):
         raise KeyError(L.gio_last_error().decode())
     return out.value
+
+
+def native_depth_shown(H, jlo, jhi, k, max_depth):
+    """The decoder's check that the depth cap cannot bind in a batch (include/gretel_io.h: gio_debug_depth_shown), for the tests:
+    H = reads per bucket (uint32), the batch's buckets jlo .. jhi, k buckets reached back.  True / False; ValueError on a bad argument."""
+    H = np.ascontiguousarray(H, dtype=np.uint32)
+    rc = io_lib().gio_debug_depth_shown(H.ctypes.data, len(H), int(jlo), int(jhi), int(k), int(max_depth))
+    if rc < 0:
+        raise ValueError(io_lib().gio_last_error().decode())
+    return bool(rc)
 
 
 PYSAM_MAX_DEPTH = 8000          # bam.pileup's default, which the reference inherits (gretel/util.py:137 passes no max_depth)

@@ -853,6 +853,27 @@ static prefetched *prefetch_take(const char *bam_path, const char *contig, int32
     return nullptr;
 }
 
+// The depth cap's shortcut (see the batch loop below): H[j] = reads that start in bucket j, a read in the buffer starts at most k
+// buckets in front of the one it is pushed in.  true: no bucket j of [jlo, jhi] has max_depth reads in H[j - k .. j] (the read
+// pushed counts as one), so the cap cannot bind there.  The caller keeps jlo >= 0 and jhi inside H.
+static bool depth_shown(const uint32_t *H, int64_t jlo, int64_t jhi, int64_t k, int32_t max_depth)
+{
+    int64_t S = 0;                                                          // sum of H[max(0, j - k) .. j]
+    for (int64_t j = jlo - k < 0 ? 0 : jlo - k; j < jlo; j++) S += H[(size_t)j];
+    for (int64_t j = jlo; j <= jhi; j++) {
+        S += H[(size_t)j];
+        if (j > jlo && j - k - 1 >= 0) S -= H[(size_t)(j - k - 1)];         // (only once the window has slid: at jlo nothing has left it)
+        if (S + 1 > (int64_t)max_depth) return false;
+    }
+    return true;
+}
+
+extern "C" int gio_debug_depth_shown(const uint32_t *H, int64_t n_buckets, int64_t jlo, int64_t jhi, int64_t k, int32_t max_depth)
+{
+    if (!H || n_buckets < 0 || jlo < 0 || jhi >= n_buckets || k < 0) return fail(-1, "bad argument");
+    return depth_shown(H, jlo, jhi, k, max_depth) ? 1 : 0;
+}
+
 static int gio_support_table_from_bam_impl(const char *bam_path, const char *contig, int32_t start_pos, int32_t end_pos,
                                            const uint8_t *region, int stepper_all, int32_t max_depth, gio_table *out,
                                            gio_alloc_fn alloc = nullptr, void *alloc_ctx = nullptr)
@@ -1155,11 +1176,13 @@ static int gio_support_table_from_bam_impl(const char *bam_path, const char *con
     };
     std::vector<std::vector<uint32_t>> lists;                               // [part][partition] -> gids, per batch
     // the depth cap's state across batches: the position the iterator stands on, the reads that entered, their ends
-    int64_t dc_pos = -1, dc_base = -1, dc_exp_upto = 0, dc_accepted = 0, dc_expired = 0;
+    // (NOWHERE: not set yet -- no position, since a malformed file may hold a mapped record in front of position 0)
+    const int64_t NOWHERE = INT64_MIN;
+    int64_t dc_pos = NOWHERE, dc_base = NOWHERE, dc_exp_upto = 0, dc_accepted = 0, dc_expired = 0;
     std::vector<uint32_t> dc_ends;                                          // [end - dc_base] reads that entered and end there
     // ... and of the showing that the cap cannot bind (below): reads per bucket of B positions from pos0 on, the longest reference
     // span, the last start, the parts whose candidates were set aside
-    struct { std::vector<uint32_t> H; int64_t pos0 = -1, B = 16, maxspan = 0, last_pos = -1; bool off = false; std::vector<size_t> deferred; } dq;
+    struct { std::vector<uint32_t> H; int64_t pos0 = INT64_MIN, B = 16, maxspan = 0, last_pos = INT64_MIN; bool off = false; std::vector<size_t> deferred; } dq;
     bool done = false;
     bool front_to_back = false;                                             // this batch again on one thread (a guessed start was wrong)
     while (!done) {
@@ -1270,31 +1293,32 @@ static int gio_support_table_from_bam_impl(const char *bam_path, const char *con
             // it would have been -- and the pass runs from there on.
             bool shown = false;
             if (!dq.off) {
-                struct pstat { int64_t first = -1, last = -1, span = 0; bool sorted = true; };
+                struct pstat { int64_t first = 0, last = 0, span = 0; bool any = false, sorted = true; };
                 std::vector<pstat> ps((size_t)n_valid);
                 worker_pool::get().run(n_valid, [&](int t) {
                     const part &P = *kept_parts[p0 + (size_t)t];
                     pstat &o = ps[(size_t)t];
                     for (size_t ci = 0; ci < P.cands.size(); ci++) {
                         const depth_cand &c = P.cands[ci];
-                        if (o.first < 0) o.first = c.pos;
-                        if ((int64_t)c.pos < o.last) o.sorted = false;
+                        if (!o.any) { o.first = c.pos; o.any = true; }
+                        else if ((int64_t)c.pos < o.last) o.sorted = false;
                         o.last = c.pos;
                         if ((int64_t)c.end - (int64_t)c.pos > o.span) o.span = (int64_t)c.end - (int64_t)c.pos;
                     }
                 });
-                bool sorted = true;
-                int64_t last = dq.last_pos, first = -1, span = dq.maxspan;
+                bool sorted = true, any = false;
+                int64_t last = dq.last_pos, first = 0, span = dq.maxspan;
                 for (int t = 0; t < n_valid; t++) {
                     const pstat &o = ps[(size_t)t];
-                    if (o.first < 0) continue;                              // (pos >= 0 on a candidate: the record is mapped)
+                    if (!o.any) continue;
                     if (!o.sorted || o.first < last) sorted = false;
-                    if (first < 0) first = o.first;
+                    if (!any) { first = o.first; any = true; }
                     last = o.last;
                     if (o.span > span) span = o.span;
                 }
-                if (sorted && first >= 0) {
-                    if (dq.pos0 < 0) {
+                // (sorted: every start of this batch lies at or behind the first start of the file, dq.pos0 -- no bucket in front of H)
+                if (sorted && any) {
+                    if (dq.pos0 == NOWHERE) {
                         dq.pos0 = first;
                         const int64_t range = (int64_t)end_pos - first + 1;
                         dq.B = 16;
@@ -1308,14 +1332,7 @@ static int gio_support_table_from_bam_impl(const char *bam_path, const char *con
                     });
                     const int64_t k = span / dq.B + 1;                      // buckets a span reaches back
                     const int64_t jlo = (first - dq.pos0) / dq.B, jhi = (last - dq.pos0) / dq.B;
-                    uint64_t S = 0;
-                    for (int64_t j = jlo - k < 0 ? 0 : jlo - k; j < jlo; j++) S += dq.H[(size_t)j];
-                    shown = true;
-                    for (int64_t j = jlo; j <= jhi && shown; j++) {
-                        S += dq.H[(size_t)j];
-                        if (j - k - 1 >= 0) S -= dq.H[(size_t)(j - k - 1)];
-                        if (S + 1 > (uint64_t)max_depth) shown = false;
-                    }
+                    shown = depth_shown(dq.H.data(), jlo, jhi, k, max_depth);
                     if (shown) { dq.last_pos = last; dq.maxspan = span; }
                 } else if (sorted) {
                     shown = true;                                           // (no candidate in this batch)
@@ -1342,7 +1359,7 @@ static int gio_support_table_from_bam_impl(const char *bam_path, const char *con
                         }
                         // what has expired is never looked at again: the histogram stays as long as the longest read span,
                         // not as long as the window (4 bytes per reference base of a chromosome otherwise)
-                        if (dc_exp_upto - dc_base > (int64_t)1 << 16 && dc_base >= 0) {
+                        if (dc_base != NOWHERE && dc_exp_upto - dc_base > (int64_t)1 << 16) {
                             const size_t k = std::min((size_t)(dc_exp_upto - dc_base), dc_ends.size());
                             dc_ends.erase(dc_ends.begin(), dc_ends.begin() + (std::ptrdiff_t)k);
                             dc_base += (int64_t)k;
@@ -1355,7 +1372,7 @@ static int gio_support_table_from_bam_impl(const char *bam_path, const char *con
                         if (c.kept_idx >= 0) { P.recs[(size_t)c.kept_idx].ch_len = 0xffffffffu; any = true; }
                         continue;
                     }
-                    if (dc_base < 0) { dc_base = c.pos; dc_exp_upto = c.pos; }
+                    if (dc_base == NOWHERE) { dc_base = c.pos; dc_exp_upto = c.pos; }
                     if ((int64_t)c.end < dc_base) { dc_accepted++; dc_expired++; continue; }     // (ends in front of everything still counted: entered and expired)
                     const size_t x = (size_t)((int64_t)c.end - dc_base);
                     if (x >= dc_ends.size()) dc_ends.resize(x + 4096, 0);

@@ -81,6 +81,15 @@ int gio_support_table_from_bam(const char *bam_path, const char *contig, int32_t
 int gio_support_table_from_bam_depth(const char *bam_path, const char *contig, int32_t start_pos, int32_t end_pos,
                                      const uint8_t *region, int stepper_all, int32_t max_depth, gio_table *out);
 void gio_table_free(gio_table *t);
+/* Diagnostics, no file: the check by which the decoder shows, batch by batch, that the cap cannot bind, so that the batch needs no
+ * sequential pass.  H[j] = reads that start in bucket j of the window (buckets of 16 positions, wider on long windows), n_buckets
+ * of them; the batch's reads start in buckets jlo .. jhi; a read in the pileup's buffer when another is pushed starts at most k
+ * buckets in front of it (k = longest reference span so far / bucket width + 1).  Returns 1 exactly when
+ *   1 + sum(H[max(0, j - k) .. j]) <= max_depth   for every j in [jlo, jhi]
+ * (the 1 is the list's sentinel node; an empty range jlo > jhi holds nothing to refute it: 1), 0 when some bucket fails it, and
+ * -1 on H == NULL, jlo < 0, jhi >= n_buckets or k < 0.  The decoder's batch loop calls the same function
+ * (tests/test_bam_depth_cap.py sweeps it against the sentence above). */
+int gio_debug_depth_shown(const uint32_t *H, int64_t n_buckets, int64_t jlo, int64_t jhi, int64_t k, int32_t max_depth);
 /* Everything of a decode that does not need the SNP positions -- header, index seek, the window's BGZF blocks read and inflated (up
  * to the inflated window's cap) -- started on a thread of the library; returns at once.  The reference's CLI parses the VCF and
  * then loads the BAM (gretel/cmd.py:69-78): a caller that knows the window before it has the SNPs calls this first and parses the

@@ -1,6 +1,7 @@
 """The native BAM decoder under AddressSanitizer + UBSan on the CPU: a valid BAM is damaged a few thousand ways
-(truncations, byte noise, blown-up length fields, unterminated names, shifted tails, flipped bits in the compressed
-stream) and every variant must come back as a status code.  Also: the index and the no-index scans agree, long-read
+(truncations, byte noise, blown-up length fields, unterminated names, shifted tails, records moved to other positions, flipped
+bits in the compressed stream) and every variant must come back as a status code, with pysam's default depth cap and with caps
+that bind.  Also: the index and the no-index scans agree, long-read
 CIGARs in the CG tag are resolved, a CIGAR that outruns its sequence is refused."""
 import os
 import struct
@@ -24,12 +25,21 @@ def test_malformed_bams_never_read_out_of_bounds(tmp_path):
     t = make_support_table(40, 300, k=4, seed=1)
     bam, vcf = str(tmp_path / "v.bam"), str(tmp_path / "v.vcf.gz")
     contig, s, e = bamio.synth_to_files(t, bam, vcf)
+    # The depth cap across batches: the three piles of tests/test_bam_depth_cap.py (the middle one across a block boundary), one
+    # block per batch, and max_depth = 450 beside the program's 1, 3 and 40 -- the first batch is set aside, the second cannot
+    # be and replays it.  Behind the piles pairs of reads out to 150 kb, so that the pass's histogram of ends is rebased.
+    from test_bam_depth_cap import _pile, _three_piles
+    piles = str(tmp_path / "piles.bam")
+    tail = [r for i in range(20) for r in _pile("t%d_" % i, 2, 5000 + 7500 * i, 100)]
+    bamio.write_bam(piles, [("c", 160_000)], _three_piles() + tail)
     # (two threads, a new part every 16 records: the per-thread parts and their merge run under the sanitizers too)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", GIO_THREADS="2", GIO_PART_RECORDS="16", GIO_WINDOW="70000")
-    for seed, src_bam, ctg, end in ((1, bam, contig, e), (2, os.path.join(REFDATA, "test.bam"), "hoot", 20)):
-        run = subprocess.run([exe, src_bam, ctg, str(end), "700", str(seed), str(tmp_path / "scratch.bam")],
-                             capture_output=True, text=True, env=env, timeout=600)
-        assert run.returncode == 0, (run.stdout[-500:], run.stderr[-3000:])
+    # (80 variants of the larger file: 4 s of the sanitized program where the two legs in front of it take 4 s and 2.5 s)
+    for seed, src_bam, ctg, end, iters, more in ((1, bam, contig, e, 700, []), (2, os.path.join(REFDATA, "test.bam"), "hoot", 20, 700, []),
+                                                 (3, piles, "c", 160_000, 80, ["1,3,40,450"])):
+        run = subprocess.run([exe, src_bam, ctg, str(end), str(iters), str(seed), str(tmp_path / "scratch.bam")] + more,
+                             capture_output=True, text=True, env=dict(env, GIO_WINDOW="65536") if more else env, timeout=600)
+        assert run.returncode == 0, (seed, run.stdout[-500:], run.stderr[-3000:])
         assert "fuzz_bam done" in run.stdout
 
 
