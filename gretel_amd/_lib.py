@@ -17,6 +17,7 @@ GH_ERR_ARG, GH_ERR_HIP, GH_ERR_BAND, GH_ERR_SYMBOL, GH_ERR_NOMEM, GH_ERR_STATE =
 GH_STORAGE = {"f32": 0, "f64": 1}
 GH_COND = {"A": 0, "B": 1, "C": 2, "D": 3, "E": 4}
 GH_BEAM_MAX = 32
+GH_VITERBI_MAX_STATES = 4096
 GH_K = {"fill": 0, "marg": 1, "lt": 2, "walk": 3, "reweight": 4, "seg": 5, "rwseg": 6}
 GH_FLOW = {0: "none", 1: "serial", 2: "seg", 3: "rwseg", 4: "fuse", 5: "pools"}      # gh_spin_plan.flow
 GH_WALK = {"seg": 0, "spec": 1, "spec1": 2, "src": 3}                                # gh_spin_plan_in.walk_mode
@@ -157,6 +158,9 @@ def load():
         "gh_beam_paths": [vp, i32, vp, vp, P(i32), P(i32)],
         "gh_beam_spin": [vp, i32, i32, dbl, vp, vp, vp, P(i32), P(i32)],
         "gh_beam_info": [vp, vp],
+        "gh_viterbi_path": [vp, vp, P(dbl), P(i32)],
+        "gh_viterbi_spin": [vp, i32, dbl, vp, vp, vp, P(i32), P(i32)],
+        "gh_viterbi_info": [vp, vp],
         "gh_coverage_sites": [i32, vp, vp, vp, i64, C.c_int32, C.c_int32, C.c_int32, vp, vp],
     }
     for name, args in sigs.items():

@@ -15,6 +15,9 @@ and, with --assign-reads (no reference counterpart; INTEGRATION.md "Read assignm
 and, with --beam B (INTEGRATION.md "Beam search"), the same files from paths that are each the best of a beam of B hypotheses over
 the chain likelihood; --beam 1 writes what a run without the flag writes.
 
+and, with --exact (INTEGRATION.md "Exact decoding"), the same files from paths that are each the global maximum of the chain
+likelihood on the matrix at that moment; a window with more than 4096 states ends the run with the library's message, status 1.
+
 and, with --score-paths / --known FASTA (INTEGRATION.md "Scoring haplotypes"), against the matrix as it was before any reweighting:
     <out>/gretel.scores   "# N L cond_mode marginal_term" + one line per recovered haplotype: i_0, ll_chain, hp_original, n_greedy,
                           n_on, first_off, min_margin, argmin_margin and the genomic position of argmin_margin
@@ -28,10 +31,12 @@ import sys
 
 from . import __version__
 from . import util
+from ._lib import GretelHipError
 from .hansel import Hansel
 
 MIN_REMOVE = 0.01          # cmd.py:157
 BEAM_MAX = 32              # include/gretel_hip.h: GH_BEAM_MAX
+EXACT_MAX_STATES = 4096    # include/gretel_hip.h: GH_VITERBI_MAX_STATES
 
 
 def build_parser():
@@ -60,6 +65,9 @@ def build_parser():
     add_score_options(p)
     p.add_argument("--beam", type=int, default=0, metavar="B", help="recover every path as the best of a beam of B hypotheses over "
                    "the chain likelihood instead of the greedy walk (1..%d; 1 = the greedy walk; 0 = off) [default: 0]" % BEAM_MAX)
+    p.add_argument("--exact", action="store_true", help="recover every path as the global maximum of the chain likelihood (exact "
+                   "decoding over S^min(L, N) states, at most %d: L <= 6 without deletion columns, L <= 5 with them) instead of "
+                   "the greedy walk" % EXACT_MAX_STATES)
     p.add_argument("--version", action="version", version="%(prog)s " + __version__)
     return p
 
@@ -166,11 +174,15 @@ def _add_path(paths, i, key, hansel_path, hp_current, hp_original, magnitude):
     rec["hp_original"].append(hp_original)
 
 
-def recover(hansel, n_snps, max_paths, log=None, beam=0):
+def recover(hansel, n_snps, max_paths, log=None, beam=0, exact=False):
     """cmd.py:148-179 on the device; returns the PATHS table in order of discovery.  The spins have already
     happened when the notes are written, but the notes are the reference's, in the reference's order.
-    beam >= 1 (--beam): every path is the best of a beam of that many hypotheses (Hansel.beam_spin)."""
-    res = hansel.beam_spin(beam, max_paths, MIN_REMOVE) if beam else hansel.spin(max_paths, MIN_REMOVE)
+    beam >= 1 (--beam): every path is the best of a beam of that many hypotheses (Hansel.beam_spin).
+    exact (--exact): every path is the global maximum of the chain likelihood (Hansel.viterbi_spin)."""
+    if exact:
+        res = hansel.viterbi_spin(max_paths, MIN_REMOVE)
+    else:
+        res = hansel.beam_spin(beam, max_paths, MIN_REMOVE) if beam else hansel.spin(max_paths, MIN_REMOVE)
     return paths_of_spin(hansel, res, log)
 
 
@@ -358,9 +370,18 @@ def check_beam_options(args):
     return None
 
 
+def check_exact_options(args):
+    """The refusals of --exact (before any BAM read or GPU call): a message, or None."""
+    if args.exact and args.beam:
+        return "--exact cannot be combined with --beam: a path is either the global maximum or the best of a beam"
+    if args.exact and debug_hpos_of(args):
+        return "--exact cannot be combined with --debughpos, which prints the branch weights of the greedy walk"
+    return None
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    bad = check_assign_options(args) or check_score_options(args) or check_beam_options(args)
+    bad = check_assign_options(args) or check_score_options(args) or check_beam_options(args) or check_exact_options(args)
     if bad:
         sys.stderr.write("[FAIL] %s\n" % bad)
         return 2
@@ -398,7 +419,13 @@ def main(argv=None):
     if debug_hpos:
         paths = recover_with_debug(hansel, vcf_h["N"], args.paths, debug_hpos)
     else:
-        paths = recover(hansel, vcf_h["N"], args.paths, beam=args.beam)
+        try:
+            paths = recover(hansel, vcf_h["N"], args.paths, beam=args.beam, exact=args.exact)
+        except GretelHipError as e:
+            if not args.exact:
+                raise
+            sys.stderr.write("[FAIL] %s\n" % e)                                   # (more states than the decoder holds: no fallback)
+            return 1
     write_outputs(paths, hansel, vcf_h, args)
     if args.assign_reads:
         write_support(paths, hansel, args)

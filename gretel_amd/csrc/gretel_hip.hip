@@ -187,6 +187,9 @@ struct gh_handle {
     void *beam_buf;        // gh_beam_paths / gh_beam_spin (beam.hpp): the beam's own table, back-pointers, path rows and scores; grows with N * L
     size_t beam_cap;
     int64_t beam_last[4];  // gh_beam_info: the last beam run on this handle
+    void *vit_buf;         // gh_viterbi_path / gh_viterbi_spin (viterbi.hpp): its own copy of the beam's table, N * states back-pointer bytes, the end row, the path
+    size_t vit_cap;
+    int64_t vit_last[4];   // gh_viterbi_info: the last exact decoding on this handle
     int cw_round_cap = env_int("GH_CW_ROUND_CAP", 0);   // =k at creation (tests): never more than k rounds per launch, so that chains stay open and the serial fallback runs
     gh_spin_plan last_plan;    // what the last gh_spin ran with (gh_debug_last_spin_plan; nothing else reads it)
     int spin_requeues;     // how often the last gh_spin rebuilt the table and queued the remaining paths again
@@ -458,7 +461,7 @@ static void free_handle(gh_handle *h)
     hipFree(h->seg_hist); hipFree(h->seg_maps); hipFree(h->seg_pmaps); hipFree(h->seg_gmaps); hipFree(h->seg_min); hipFree(h->lmsel1); hipFree(h->spin_lmsel);
     hipFree(h->seg_smin); hipFree(h->seg_gmin); hipFree(h->cm5snap); hipFree(h->seg_halo);
     if (h->stage) hipHostFree(h->stage);
-    hipFree(h->ew_buf); hipFree(h->asg_buf); hipFree(h->score_buf); hipFree(h->beam_buf);
+    hipFree(h->ew_buf); hipFree(h->asg_buf); hipFree(h->score_buf); hipFree(h->beam_buf); hipFree(h->vit_buf);
     hipFree(h->cw_keys_d); hipFree(h->cw_exits_d); hipFree(h->cw_pend_d); hipFree(h->cw_pend_exit_d);
     hipFree(h->cw_pend_exit); hipFree(h->cw_pend_ready); hipFree(h->cw_phist);
     hipFree(h->cw_keys); hipFree(h->cw_exits); hipFree(h->cw_hist); hipFree(h->cw_last_hit); hipFree(h->cw_npool); hipFree(h->cw_walked); hipFree(h->cw_nxt); hipFree(h->cw_true); hipFree(h->cw_pend); hipFree(h->cw_npend);
@@ -3397,3 +3400,5 @@ extern "C" int gh_profile_bytes(gh_t *h, int kernel, double *bytes_per_launch)
 #include "score.hpp"
 // beam search over the chain likelihood (gh_beam_paths, gh_beam_spin, gh_beam_info) ------------------
 #include "beam.hpp"
+// exact decoding of the chain likelihood (gh_viterbi_path, gh_viterbi_spin, gh_viterbi_info) -----------
+#include "viterbi.hpp"

@@ -394,6 +394,45 @@ class Hansel:
         check(self._lib.gh_beam_info(self._h, _p(out)))
         return tuple(int(v) for v in out)
 
+    def viterbi_path(self):
+        """The full path of largest chain likelihood on the tensor as it is now, exactly (gh_viterbi_path; the definition and
+        the tie rule: INTEGRATION.md "Exact decoding").  Returns dict(path uint8[N+1], ll_chain, hole_at); at a hole path and
+        ll_chain are None.  Served where S^min(L, N) <= 4096 states (S = the candidate symbols the window offers); beyond that
+        GretelHipError, and the beam is the tool.  The tensor is not touched."""
+        self._ensure()
+        path = np.zeros(self.n + 1, dtype=np.uint8)
+        ll, hole = C.c_double(), C.c_int()
+        check(self._lib.gh_viterbi_path(self._h, _p(path), C.byref(ll), C.byref(hole)))
+        if hole.value:
+            return dict(path=None, ll_chain=None, hole_at=hole.value)
+        return dict(path=path, ll_chain=ll.value, hole_at=0)
+
+    def viterbi_spin(self, max_paths=100, min_remove=0.01):
+        """gretel/cmd.py:148-179 with the exact path in place of generate_path (gh_viterbi_spin: a host loop, not the
+        throughput path).  Returns beam_spin()'s dict: ll_chain float64[n] is the exact maximum when each path was found."""
+        self._ensure()
+        nrec = C.sizeof(_lib.gh_path_rec) // 8
+        paths = np.empty((max(0, max_paths), self.n + 1), dtype=np.uint8)
+        recs = np.empty((max(1, max_paths), nrec), dtype=np.float64)
+        ll = np.zeros(max(1, max_paths))
+        n, hole = C.c_int(), C.c_int()
+        check(self._lib.gh_viterbi_spin(self._h, int(max_paths), float(min_remove), _p(paths), _p(recs), _p(ll),
+                                        C.byref(n), C.byref(hole)))
+        k = n.value
+        if k:
+            self.is_weighted = True
+        r = recs[:k]
+        return dict(n=k, hole_at=hole.value, paths=paths[:k], hp_current=r[:, 0].copy(), hp_original=r[:, 1].copy(),
+                    ratio=r[:, 2].copy(), magnitude=r[:, 3].copy(), min_marginal=r[:, 4].copy(), ll_chain=ll[:k].copy())
+
+    def viterbi_info(self):
+        """The last exact decoding on this handle (gh_viterbi_info): (S candidate symbols, Le = min(L, N), states = S^Le,
+        bytes of the decoder's device scratch)."""
+        self._ensure()
+        out = np.zeros(4, dtype=np.int64)
+        check(self._lib.gh_viterbi_info(self._h, _p(out)))
+        return tuple(int(v) for v in out)
+
     def clear(self):
         self._staged = []
         if self._h is not None:

@@ -315,6 +315,44 @@ int gh_beam_spin(gh_t *h, int width, int max_paths, double min_remove, uint8_t *
                  gh_path_rec *recs, double *ll_chain /*[max_paths], may be NULL*/, int *n_out, int *hole_at);
 int gh_beam_info(const gh_t *h, int64_t out[4]);
 
+/* Exact decoding of the chain likelihood (no reference counterpart; INTEGRATION.md "Exact decoding").  The beam can only say that a
+ * better path than the greedy one exists; this says what the best one is.  Notation as above: cm(p) the candidate set at SNP p,
+ * w_p(c | x) the weight gh_edge_weights_at(h, p, x, ...) returns for c (the marginal term first, then lags 1, 2, ... in that
+ * order), q(c) the index of c in the handle's cand_order, Le = min(L, N).
+ *   A full path x has x[0] = '_' and x[p] in cm(p) for p = 1..N.  score(x) is the sequential binary64 sum of w_p(x[p] | x) in
+ *   ascending p from +0.0: exactly the ll_chain of gh_score_paths(x).
+ *   Result: ll = the maximum of score(x) over all full paths, attained exactly: a weight depends on the last Le picks only, so the
+ *   chain likelihood is a Markov score of order Le, and fl(a + w) is monotone in a -- keeping the best prefix per state (the last
+ *   Le picks) loses nothing.
+ *   Tie rule: the path returned is the one this procedure keeps.  After step p two prefixes compete when they agree on positions
+ *   p-Le+1..p.  For p > Le they then differ at position p-Le: they are taken in ascending q(x[p-Le]); the first stays and is
+ *   replaced only by a strictly larger score (plain IEEE >; the arg-max rule of gretel/gretel.py:159-174).  For p <= Le nothing
+ *   competes.  At p = N the surviving prefixes are taken in ascending lexicographic order of (q(x[N]), q(x[N-1]), ...,
+ *   q(x[N-Le+1])); the first stays unless strictly beaten.
+ *   Hole: at the first p with empty cm(p), hole_at = p and neither path nor score is written.  Otherwise hole_at = 0.
+ *   State space: U = the union over p = 1..N of the candidate symbols offered, S = |U| (4 in a window without deletion columns);
+ *   the states number S^Le.  The decoder serves S^Le <= GH_VITERBI_MAX_STATES: L <= 6 without deletion columns, L <= 5 with them,
+ *   L <= 12 in biallelic windows -- 4096 is the largest power of four whose two score rows (64 KB) leave the table ring room in
+ *   on-chip memory.  Beyond it the call is refused; the beam remains the tool for larger L.
+ * GH_ERR_ARG for a null argument (ll_chain of gh_viterbi_spin may be NULL), max_paths < 0, a handle created with offer_zero (a
+ * zero-count candidate can weigh NaN, which no order ranks) or S^Le > GH_VITERBI_MAX_STATES (the message names S, Le and the
+ * count).  GH_ERR_STATE before any fill, add or import.  GH_ERR_NOMEM when the scratch cannot be had: a block of the handle of
+ * its own, kept until gh_destroy -- the beam's table, N * (30 Le + 6) * 8 bytes, and one back-pointer byte per position and
+ * state, (N + 1) * S^Le bytes (10 MB at 10k SNPs and 1024 states, 41 MB at 4096).
+ * gh_viterbi_path only reads the tensor: the band, L, the fill statistics, the snapshot, the handle's conditional tables and the
+ * results of a following gh_spin stay as they are, bit for bit.
+ * gh_viterbi_spin is gh_beam_spin with the exact path in place of the beam's rank-0 path: per path, decode; hp_current,
+ * hp_original (under the snapshot, taken now if there is none) and min_marginal as gh_score_paths gives them on the tensor at
+ * that moment; ratio = max(min_marginal, min_remove); magnitude = the removed mass of gh_reweight_path; it stops at the first
+ * hole.  ll_chain[s] = the exact maximum when path s was found.  A host loop, NOT the throughput path.
+ * gh_viterbi_info, the last decoding on the handle: out[0] = S, out[1] = Le, out[2] = states = S^Le, out[3] = bytes of the
+ * decoder's device scratch (all 0 before the first). */
+#define GH_VITERBI_MAX_STATES 4096
+int gh_viterbi_path(gh_t *h, uint8_t *path_out /*[N+1]*/, double *ll_chain, int *hole_at);
+int gh_viterbi_spin(gh_t *h, int max_paths, double min_remove, uint8_t *paths_out /*[max_paths][N+1]*/,
+                    gh_path_rec *recs, double *ll_chain /*[max_paths], may be NULL*/, int *n_out, int *hole_at);
+int gh_viterbi_info(const gh_t *h, int64_t out[4]);
+
 /* tensor export/import for --dumpmatrix (gretel/cmd.py:81-82) and tests:
  * band layout [(N+2)][band][7][7] as doubles; dense layout [7][7][N+2][N+2] (gretel/cmd.py:76-77). */
 int gh_export_band(gh_t *h, double *out);
