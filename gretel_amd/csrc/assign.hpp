@@ -207,11 +207,8 @@ extern "C" int gh_assign_reads(gh_t *h, const gh_reads_t *r, const uint8_t *path
     if (r->dev != h->dev) return fail(GH_ERR_ARG, "reads live on device %d, handle on %d", r->dev, h->dev);
     const int N = h->N;
     const size_t path_bytes = (size_t)n_paths * (size_t)(N + 1);
-    uint8_t top = 0;
-    for (size_t q = 0; q < path_bytes; q++) top = std::max(top, paths[q]);
-    if (top > 6)
-        for (size_t q = 0; q < path_bytes; q++)
-            if (paths[q] > 6) return fail(GH_ERR_ARG, "path %d holds %d at SNP %d: not a symbol index", (int)(q / (N + 1)), paths[q], (int)(q % (N + 1)));
+    int rc = check_symbol_rows(paths, n_paths, (size_t)N + 1, GH_ERR_ARG);
+    if (rc) return rc;
     // planes of the bit-sliced counters: enough for the longest read's column count
     int np = 1;
     while (np < 31 && (1ll << np) <= (long long)r->max_k) np++;
@@ -219,40 +216,25 @@ extern "C" int gh_assign_reads(gh_t *h, const gh_reads_t *r, const uint8_t *path
     if (set_dev(h)) return GH_ERR_HIP;
 
     // one device block, kept on the handle: counters [3][n_paths], totals [8], paths, masks [nw][N+1][5], per-read [3][n_reads]
+    // (assign_layout)
     const int nw = (n_paths + 63) / 64;
     if (nw > 65535) return fail(GH_ERR_ARG, "n_paths %d: at most %d", n_paths, 65535 * 64);
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t cnt_b = up((size_t)3 * n_paths * 8 + 8 * 8);
-    const size_t path_b = up(path_bytes);
-    const size_t mask_b = up((size_t)nw * (size_t)(N + 1) * 5 * 8);
-    const size_t read_b = per_read ? up((size_t)r->n_reads * 3 * 4) : 0;
-    const size_t need = cnt_b + path_b + mask_b + read_b;
-    if (need > h->asg_cap) {
-        HIPCHK(hipStreamSynchronize(h->stream));
-        hipFree(h->asg_buf);
-        h->asg_buf = nullptr;
-        h->asg_cap = 0;
-        HIPCHK(hipMalloc(&h->asg_buf, need));
-        h->asg_cap = need;
-    }
-    char *base = (char *)h->asg_buf;
-    unsigned long long *cnt = (unsigned long long *)base;
-    unsigned long long *tot = cnt + 3 * (size_t)n_paths;
-    uint8_t *d_paths = (uint8_t *)(base + cnt_b);
-    unsigned long long *mask = (unsigned long long *)(base + cnt_b + path_b);
-    int32_t *d_read = per_read ? (int32_t *)(base + cnt_b + path_b + mask_b) : nullptr;
+    const size_t need = assign_layout(nullptr, n_paths, N, r->n_reads, per_read).total;
+    if ((rc = scratch_reserve(h, &h->asg, need, "gh_assign_reads: the scratch of the paths' counters and masks and the per-read results"))) return rc;
+    const assign_bufs d = assign_layout(h->asg.buf, n_paths, N, r->n_reads, per_read);
+    unsigned long long *cnt = d.cnt, *tot = cnt + 3 * (size_t)n_paths, *mask = d.mask;
 
     HIPCHK(hipMemsetAsync(cnt, 0, (size_t)3 * n_paths * 8 + 8 * 8, h->stream));
     if (n_paths > 0) {
-        HIPCHK(hipMemcpyAsync(d_paths, paths, path_bytes, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(d.paths, paths, path_bytes, hipMemcpyHostToDevice, h->stream));
         hipLaunchKernelGGL(k_assign_masks, dim3((unsigned)((N + 1 + ASSIGN_BLOCK - 1) / ASSIGN_BLOCK), (unsigned)nw), dim3(ASSIGN_BLOCK), 0,
-                           h->stream, d_paths, n_paths, N, mask);
-        { int rc_ = post_launch(h, "k_assign_masks"); if (rc_) return rc_; }
+                           h->stream, d.paths, n_paths, N, mask);
+        if ((rc = post_launch(h, "k_assign_masks"))) return rc;
     }
     if (r->n_reads > 0) {
         // eight workgroups of 256 lanes per CU at most; the per-haplotype counters leave each workgroup once
         const unsigned grid = (unsigned)std::min<int64_t>((r->n_reads + ASSIGN_BLOCK - 1) / ASSIGN_BLOCK, 2048);
-#define ASSIGN_NP(K_) assign_launch<K_>(h->stream, grid, r, mask, n_paths, N, min_snps, max_mismatch, cnt, d_read, tot)
+#define ASSIGN_NP(K_) assign_launch<K_>(h->stream, grid, r, mask, n_paths, N, min_snps, max_mismatch, cnt, d.read, tot)
         switch (NP) {
         case 2: ASSIGN_NP(2); break;
         case 3: ASSIGN_NP(3); break;
@@ -264,7 +246,7 @@ extern "C" int gh_assign_reads(gh_t *h, const gh_reads_t *r, const uint8_t *path
         default: ASSIGN_NP(32); break;
         }
 #undef ASSIGN_NP
-        { int rc_ = post_launch(h, "k_assign"); if (rc_) return rc_; }
+        if ((rc = post_launch(h, "k_assign"))) return rc;
     }
     unsigned long long htot[8];
     HIPCHK(hipMemcpyAsync(htot, tot, sizeof htot, hipMemcpyDeviceToHost, h->stream));
@@ -275,9 +257,9 @@ extern "C" int gh_assign_reads(gh_t *h, const gh_reads_t *r, const uint8_t *path
     }
     if (per_read && r->n_reads > 0) {
         const size_t b = (size_t)r->n_reads * 4;
-        if (read_hap) HIPCHK(hipMemcpyAsync(read_hap, d_read, b, hipMemcpyDeviceToHost, h->stream));
-        if (read_best) HIPCHK(hipMemcpyAsync(read_best, d_read + r->n_reads, b, hipMemcpyDeviceToHost, h->stream));
-        if (read_informative) HIPCHK(hipMemcpyAsync(read_informative, d_read + 2 * r->n_reads, b, hipMemcpyDeviceToHost, h->stream));
+        if (read_hap) HIPCHK(hipMemcpyAsync(read_hap, d.read, b, hipMemcpyDeviceToHost, h->stream));
+        if (read_best) HIPCHK(hipMemcpyAsync(read_best, d.read + r->n_reads, b, hipMemcpyDeviceToHost, h->stream));
+        if (read_informative) HIPCHK(hipMemcpyAsync(read_informative, d.read + 2 * r->n_reads, b, hipMemcpyDeviceToHost, h->stream));
     }
     HIPCHK(hipStreamSynchronize(h->stream));
     if (htot[4]) return fail(GH_ERR_SYMBOL, "gh_assign_reads: %llu read(s) carry a byte outside \"ACGTN-_\"", htot[4]);

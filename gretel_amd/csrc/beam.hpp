@@ -3,12 +3,7 @@
 // binary64 sum in ascending p and every weight k_score_pos' additions in k_score_pos' order, so what comes out is what
 // gh_score_paths says of the same paths bit for bit, and B = 1 is gh_generate_path.  The tensor is only read.
 //
-//   k_beam_table  (parallel) the beam's own plain table in its own scratch block, never the handle's G (which may be ranked, may
-//                 carry the marginal term, may be mid-way through an incremental refresh):  per source position i one block of
-//                 30 L + 6 doubles,  Gb[i][a6][l-1][b5] = lt_entry(bake_lm = 0)  and behind them what target i + 1 needs besides:
-//                 its five log10 marginals (minfo[i+1][0..4]) and its candidate bits (minfo[i+1][10]).  With that header the
-//                 walk's whole input is ONE contiguous stream in source order.  (The issue's sketch had the bare 30 L doubles
-//                 and LT_PAD zero blocks behind N: the header saves the walk a second stream, and no reader overruns N sources.)
+//   k_beam_table  chain_table.hpp: the plain table, one block of 30 L + 6 doubles per source position, in the beam's own scratch block
 //   k_beam_walk   one workgroup, N dependent steps.  Eight lanes per hypothesis, lane s < 5 = candidate b5 = s (k_score_pos'
 //                 grouping): a child lane sums its weight, adds it to its parent's score, puts the key (score, w) into LDS;
 //                 behind a barrier it counts the children that precede it in the total order (score desc, parent rank asc, w
@@ -27,7 +22,6 @@
 // ---------------------------------------------------------------------------------------------
 
 #define BEAM_KEYS (GH_BEAM_MAX * 5)
-#define BEAM_LDS_MAX (160 * 1024)  /* LDS one workgroup can have on gfx950 */
 #define BEAM_AHEAD_MIN 16          /* staged only where the loader can run this many steps ahead: a step is a few LDS round trips and
                                       two barriers, a block from HBM a few of those -- 16 leaves it room under load */
 #define BEAM_AHEAD_MAX 64          /* ... and never more: nothing is gained, and a short window would be preloaded whole */
@@ -35,7 +29,6 @@
 #define BEAM_MAX_L 2048            /* the two ring buffers of 32 hypotheses stay within the LDS */
 #define BEAM_TRACE_POS 1024
 
-__host__ __device__ constexpr int beam_src_doubles(int L) { return 30 * L + 6; }
 __host__ __device__ constexpr int beam_ring_bytes(int L) { return (L + 3) & ~3; }             // one hypothesis' ring, whole words
 // keys, two score rows, two ring buffers
 __host__ __device__ constexpr size_t beam_fixed_lds(int L) { return (size_t)BEAM_KEYS * 16 + 2 * GH_BEAM_MAX * 8 + 2 * (size_t)GH_BEAM_MAX * beam_ring_bytes(L); }
@@ -49,44 +42,6 @@ __host__ __device__ constexpr int beam_ring_sources(int L)
 }
 static_assert(beam_ring_sources(3) == 68 && beam_ring_sources(16) >= 16 + 17 && beam_ring_sources(20) == 0, "the staged path covers L <= 16");
 static_assert(beam_fixed_lds(BEAM_MAX_L) < BEAM_LDS_MAX, "the rings of the longest history fit");
-
-struct beam_out {
-    int n_out, hole_at;
-    int end, rows;     // what k_beam_trace follows: `rows` hypotheses from position `end` down
-};
-
-template <typename T>
-__global__ void __launch_bounds__(256)
-k_beam_table(const T *__restrict__ band, const T *__restrict__ tband, int N, int W, int L, int cond_mode,
-             const double *__restrict__ cnt, const int32_t *__restrict__ nvalid, const uint32_t *__restrict__ cmask,
-             const double *__restrict__ minfo, symmap sm, double *__restrict__ Gb)
-{
-    const int sd = beam_src_doubles(L);
-    const size_t total = (size_t)N * sd, gsize = (size_t)gridDim.x * blockDim.x;
-    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += gsize) {
-        const int i = (int)(t / sd), q = (int)(t % sd);
-        double v;
-        if (q < 30 * L) {
-            const int b5 = q % LT_ROW, r = q / LT_ROW;
-            v = lt_entry(band, N, W, cond_mode, 0, cnt, nvalid, cmask, minfo, i, r / L, r % L + 1, b5, sm, tband);
-        } else {
-            const int hq = q - 30 * L;                       // target i + 1 <= N: its log10 marginals, then its candidate bits
-            v = minfo[(size_t)(i + 1) * MINFO + (hq < 5 ? hq : 10)];
-        }
-        Gb[t] = v;
-    }
-}
-
-// The walk's barrier orders LDS only: __syncthreads() also waits for every global access in flight (vmcnt(0)), which would drain
-// the loader's block and the step's back-pointer store twice a step.  Nothing k_beam_walk writes to global memory is read inside
-// it, and what it reads there nobody writes, so the workgroup needs no order on global memory.  (Measured, DESIGN.md 4.9: by
-// itself this did not move the time of a step -- the loader's own wait for its block still stands behind the back-pointer store.)
-__device__ __forceinline__ void beam_barrier()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
 
 // B hypotheses, 8 lanes each (at least one wavefront); dynamic LDS: [R blocks (STAGED)] [keys] [scores 2 x 32] [rings 2 x 32 x Lr]
 template <bool STAGED>
@@ -243,22 +198,13 @@ k_beam_trace(const uint8_t *__restrict__ bp, int bps, int N, const beam_out *__r
     }
 }
 
-// host ----------------------------------------------------------------------------------------
-struct beam_bufs {
-    double *Gb;
-    uint8_t *bp, *paths;
-    double *ll;
-    beam_out *out;
-    int bps;
-};
-
+// host ---------------------------------------------------------------------------------------- (beam_out, beam_bufs: scratch_layout.hpp)
 static int beam_check(const gh_handle *h, int width, const char *who)
 {
     if (width < 1 || width > GH_BEAM_MAX) return fail(GH_ERR_ARG, "%s: width must be 1..%d (got %d)", who, GH_BEAM_MAX, width);
-    if (h->cfg.offer_zero)
-        return fail(GH_ERR_ARG, "%s: the handle offers zero-count candidates (offer_zero), whose weights can be NaN (-inf + +inf): no order ranks them", who);
-    if (h->band_zero) return fail(GH_ERR_STATE, "%s before any fill or import: the tensor holds no evidence", who);
-    const int Le = h->L < h->N ? h->L : h->N;
+    int rc = decode_check(h, who);
+    if (rc) return rc;
+    const int Le = chain_lags(h);
     if (Le > BEAM_MAX_L) return fail(GH_ERR_ARG, "%s: the beam keeps %d-symbol histories in LDS: L up to %d", who, Le, BEAM_MAX_L);
     return GH_OK;
 }
@@ -266,44 +212,13 @@ static int beam_check(const gh_handle *h, int width, const char *who)
 // one beam over the tensor as it stands: the results stay in the handle's beam scratch (`b`), *ho = counts and hole
 static int beam_run(gh_handle *h, int width, beam_bufs *b, beam_out *ho)
 {
-    const int N = h->N;
-    // (lags beyond the window's first position are never summed: a table of min(L, N) lags gives the same weights)
-    const int L = h->L < N ? h->L : N;
-    int rc = ensure_marg(h);
+    const int N = h->N, L = chain_lags(h);
+    const size_t table_doubles = (size_t)N * beam_src_doubles(L);
+    const size_t need = beam_layout(nullptr, N, table_doubles, width).total;
+    int rc = scratch_reserve(h, &h->beam, need, "the beam's scratch, which grows with N * L,");
     if (rc) return rc;
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const int bps = (width + 3) & ~3;
-    const size_t n1 = (size_t)N + 1;
-    const size_t gb_b = up((size_t)N * beam_src_doubles(L) * 8), bp_b = up(n1 * bps), path_b = up(n1 * GH_BEAM_MAX);
-    const size_t need = gb_b + bp_b + path_b + up(GH_BEAM_MAX * 8) + up(sizeof(beam_out));
-    if (need > h->beam_cap) {
-        HIPCHK(hipStreamSynchronize(h->stream));
-        hipFree(h->beam_buf);
-        h->beam_buf = nullptr;
-        h->beam_cap = 0;
-        if (hipMalloc(&h->beam_buf, need) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(GH_ERR_NOMEM, "the beam's scratch (%zu bytes: it grows with N * L) cannot be had", need);
-        }
-        h->beam_cap = need;
-    }
-    char *base = (char *)h->beam_buf;
-    b->Gb = (double *)base;
-    b->bp = (uint8_t *)(base + gb_b);
-    b->paths = b->bp + bp_b;
-    b->ll = (double *)(b->paths + path_b);
-    b->out = (beam_out *)((char *)b->ll + up(GH_BEAM_MAX * 8));
-    b->bps = bps;
-
-    const void *tb = (h->tband && h->tband_epoch == h->band_epoch) ? h->tband : nullptr;
-    const size_t total = (size_t)N * beam_src_doubles(L);
-    const unsigned nb = (unsigned)std::min<size_t>((total + 255) / 256, 256 * 16);
-    with_storage(h, [&](auto z) {
-        using T = decltype(z);
-        hipLaunchKernelGGL(k_beam_table<T>, dim3(nb), dim3(256), 0, h->stream, (const T *)h->band, (const T *)tb, N, h->W, L, h->cfg.cond_mode,
-                           h->cnt, h->nvalid, h->cmask, h->minfo, h->sm, b->Gb);
-    });
-    if ((rc = post_launch(h, "k_beam_table"))) return rc;
+    *b = beam_layout(h->beam.buf, N, table_doubles, width);
+    if ((rc = chain_table_build(h, L, b->Gb))) return rc;
 
     static const bool no_stage = env_off("GH_BEAM_STAGE");      // (A/B: every L through the global loader)
     const int R = no_stage ? 0 : beam_ring_sources(L);
@@ -313,21 +228,18 @@ static int beam_run(gh_handle *h, int width, beam_bufs *b, beam_out *ho)
     if (R) {
         lds_limit<k_beam_walk<true>>(lds, h->dev);
         hipLaunchKernelGGL(k_beam_walk<true>, dim3(1), dim3(threads), lds, h->stream, (const double *)b->Gb, N, L, width, h->cfg.marginal_term, R,
-                           b->bp, bps, b->ll, b->out);
+                           b->bp, b->bps, b->ll, b->out);
     } else {
         lds_limit<k_beam_walk<false>>(lds, h->dev);
         hipLaunchKernelGGL(k_beam_walk<false>, dim3(1), dim3(threads), lds, h->stream, (const double *)b->Gb, N, L, width, h->cfg.marginal_term, L + 2,
-                           b->bp, bps, b->ll, b->out);
+                           b->bp, b->bps, b->ll, b->out);
     }
     if ((rc = post_launch(h, "k_beam_walk"))) return rc;
-    hipLaunchKernelGGL(k_beam_trace, dim3(1), dim3(256), 0, h->stream, (const uint8_t *)b->bp, bps, N, (const beam_out *)b->out, h->sm, b->paths);
+    hipLaunchKernelGGL(k_beam_trace, dim3(1), dim3(256), 0, h->stream, (const uint8_t *)b->bp, b->bps, N, (const beam_out *)b->out, h->sm, b->paths);
     if ((rc = post_launch(h, "k_beam_trace"))) return rc;
     HIPCHK(hipMemcpyAsync(ho, b->out, sizeof *ho, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->beam_last[0] = R ? 1 : 0;
-    h->beam_last[1] = R;
-    h->beam_last[2] = threads;
-    h->beam_last[3] = (int64_t)need;
+    h->beam_last[0] = R ? 1 : 0; h->beam_last[1] = R; h->beam_last[2] = threads; h->beam_last[3] = (int64_t)need;
     return GH_OK;
 }
 
@@ -361,33 +273,15 @@ extern "C" int gh_beam_spin(gh_t *h, int width, int max_paths, double min_remove
     int rc = beam_check(h, width, "gh_beam_spin");
     if (rc) return rc;
     if (set_dev(h)) return GH_ERR_HIP;
-    *n_out = 0; *hole_at = 0;
-    if (max_paths == 0) return GH_OK;
-    if (!h->have_orig && (rc = gh_snapshot_original(h))) return rc;
-    const size_t n1 = (size_t)h->N + 1;
-    for (int s = 0; s < max_paths; s++) {
+    return decode_spin(h, max_paths, min_remove, paths_out, recs, ll_chain, n_out, hole_at, [&](decoded *d) -> int {
         beam_bufs b;
         beam_out ho;
         if ((rc = beam_run(h, width, &b, &ho))) return rc;
-        if (ho.hole_at) { *hole_at = ho.hole_at; break; }
-        uint8_t *path = paths_out + n1 * s;
-        double ll = 0.0;
-        HIPCHK(hipMemcpyAsync(path, b.paths, n1, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipMemcpyAsync(&ll, b.ll, 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        // the record of that path on the tensor as it stands (hp_original under the snapshot), then the reweight
-        gh_score_rec sr;
-        if ((rc = gh_score_paths(h, path, 1, &sr, nullptr, nullptr, nullptr))) return rc;
-        gh_path_rec &r = recs[s];
-        r.hp_current = sr.hp_current;
-        r.hp_original = sr.hp_original;
-        r.min_marginal = sr.min_marginal;
-        r.ratio = sr.min_marginal < min_remove ? min_remove : sr.min_marginal;
-        if ((rc = gh_reweight_path(h, path, r.ratio, &r.magnitude))) return rc;
-        if (ll_chain) ll_chain[s] = ll;
-        *n_out = s + 1;
-    }
-    return GH_OK;
+        d->hole = ho.hole_at;
+        d->d_path = b.paths;                                   // (rank 0: the best hypothesis and its score)
+        d->d_ll = b.ll;
+        return GH_OK;
+    });
 }
 
 extern "C" int gh_beam_info(const gh_t *h, int64_t out[4])

@@ -36,6 +36,7 @@
 
 #include "gretel_hip.h"
 #include "gh_detlog.h"
+#include "scratch_layout.hpp"
 
 
 // ---------------------------------------------------------------------------------------------
@@ -99,6 +100,11 @@ static int walk_mode_from_env()
     if (!strcmp(m, "src")) return WM_SRC;
     return WM_SPEC;
 }
+
+struct dev_scratch {       // a device block that grows on demand (scratch_reserve); free_handle frees it
+    void *buf;
+    size_t cap;
+};
 
 // gh_create value-initialises the handle: what is not given a value here starts at zero / null / false
 struct gh_handle {
@@ -180,15 +186,13 @@ struct gh_handle {
     uint8_t *stage;        // pinned host staging for the results of a spin
     size_t stage_cap;
     double *ew_buf;        // gh_edge_weights_at: seven weights and the candidate mask
-    void *asg_buf;         // gh_assign_reads (assign.hpp): counters, paths, match masks and per-read results, grown on demand
-    size_t asg_cap;
-    void *score_buf;       // gh_score_paths (score.hpp): one slab's paths, records and per-position values, grown on demand
-    size_t score_cap;
-    void *beam_buf;        // gh_beam_paths / gh_beam_spin (beam.hpp): the beam's own table, back-pointers, path rows and scores; grows with N * L
-    size_t beam_cap;
+    // four scratch blocks, each grown on demand (scratch_reserve) and laid out by its user's function in scratch_layout.hpp.  Four,
+    // not one arena: gh_beam_spin and gh_viterbi_spin call gh_score_paths while the decoder's block still holds the path row
+    dev_scratch asg;       // gh_assign_reads (assign.hpp): counters, paths, match masks and per-read results
+    dev_scratch score;     // gh_score_paths (score.hpp): one slab's paths, records and per-position values
+    dev_scratch beam;      // gh_beam_paths / gh_beam_spin (beam.hpp): its chain table, back-pointers, path rows and scores; grows with N * L
     int64_t beam_last[4];  // gh_beam_info: the last beam run on this handle
-    void *vit_buf;         // gh_viterbi_path / gh_viterbi_spin (viterbi.hpp): its own copy of the beam's table, N * states back-pointer bytes, the end row, the path
-    size_t vit_cap;
+    dev_scratch vit;       // gh_viterbi_path / gh_viterbi_spin (viterbi.hpp): its chain table, N * states back-pointer bytes, the end row, the path
     int64_t vit_last[4];   // gh_viterbi_info: the last exact decoding on this handle
     int cw_round_cap = env_int("GH_CW_ROUND_CAP", 0);   // =k at creation (tests): never more than k rounds per launch, so that chains stay open and the serial fallback runs
     gh_spin_plan last_plan;    // what the last gh_spin ran with (gh_debug_last_spin_plan; nothing else reads it)
@@ -341,6 +345,27 @@ static int post_launch(gh_handle *h, const char *what)
     return GH_OK;
 }
 
+// the to-major copy while it mirrors the band (nullptr otherwise): a column sum is then a contiguous run, same addends in the same order
+static const void *tband_current(const gh_handle *h) { return (h->tband && h->tband_epoch == h->band_epoch) ? h->tband : nullptr; }
+
+// a scratch block that holds `need` bytes: kept while it is large enough, otherwise freed and had anew once the stream has drained
+// (what it held is gone).  A block that cannot be had is GH_ERR_NOMEM, and not left behind as HIP's last error for the next
+// post_launch of this thread to find.
+static int scratch_reserve(gh_handle *h, dev_scratch *s, size_t need, const char *what)
+{
+    if (need <= s->cap) return GH_OK;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    hipFree(s->buf);
+    s->buf = nullptr;
+    s->cap = 0;
+    if (hipMalloc(&s->buf, need) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(GH_ERR_NOMEM, "%s cannot be had (%zu bytes)", what, need);
+    }
+    s->cap = need;
+    return GH_OK;
+}
+
 // profiling brackets --------------------------------------------------------------------------
 static void prof_begin(gh_handle *h, int k)
 {
@@ -461,7 +486,7 @@ static void free_handle(gh_handle *h)
     hipFree(h->seg_hist); hipFree(h->seg_maps); hipFree(h->seg_pmaps); hipFree(h->seg_gmaps); hipFree(h->seg_min); hipFree(h->lmsel1); hipFree(h->spin_lmsel);
     hipFree(h->seg_smin); hipFree(h->seg_gmin); hipFree(h->cm5snap); hipFree(h->seg_halo);
     if (h->stage) hipHostFree(h->stage);
-    hipFree(h->ew_buf); hipFree(h->asg_buf); hipFree(h->score_buf); hipFree(h->beam_buf); hipFree(h->vit_buf);
+    hipFree(h->ew_buf); hipFree(h->asg.buf); hipFree(h->score.buf); hipFree(h->beam.buf); hipFree(h->vit.buf);
     hipFree(h->cw_keys_d); hipFree(h->cw_exits_d); hipFree(h->cw_pend_d); hipFree(h->cw_pend_exit_d);
     hipFree(h->cw_pend_exit); hipFree(h->cw_pend_ready); hipFree(h->cw_phist);
     hipFree(h->cw_keys); hipFree(h->cw_exits); hipFree(h->cw_hist); hipFree(h->cw_last_hit); hipFree(h->cw_npool); hipFree(h->cw_walked); hipFree(h->cw_nxt); hipFree(h->cw_true); hipFree(h->cw_pend); hipFree(h->cw_npend);
@@ -1008,7 +1033,7 @@ static int ensure_lt(gh_handle *h, bool baked = false, bool derived = true, bool
     size_t nb = (total + block - 1) / block;
     if (nb > 256 * 16) nb = 256 * 16;
     // (column conditionals: the to-major copy, while it mirrors the band, makes the column sums contiguous reads)
-    const void *tb_lt = (h->tband && h->tband_epoch == h->band_epoch) ? h->tband : nullptr;
+    const void *tb_lt = tband_current(h);
     lt_args a;
     a.band = h->band; a.N = h->N; a.W = h->W; a.L = h->L; a.cond_mode = h->cfg.cond_mode; a.bake_lm = want_baked ? 1 : 0;
     a.cnt = h->cnt; a.nvalid = h->nvalid; a.cmask = h->cmask; a.minfo = h->minfo; a.G = h->lt; a.st = h->dstate; a.inc_path = inc;
@@ -3007,7 +3032,7 @@ static int batch_finish(gh_batch *b, const std::vector<int> &ws, const std::vect
         gh_handle *h = b->hs[w];
         n_out[w] = hs[w].n_done;
         hole_at[w] = hs[w].stop ? hs[w].hole_at : 0;
-        const bool kept = h->tband && h->tband_epoch == h->band_epoch &&
+        const bool kept = tband_current(h) &&
                           (hs[w].pipe_status == PIPE_DONE || hs[w].pipe_status == PIPE_ABORTED) &&
                           (h->cfg.cond_mode == GH_COND_C || h->cfg.cond_mode == GH_COND_E);
         h->dirty_marg = h->dirty_lt = true; h->band_epoch++;
@@ -3394,10 +3419,24 @@ extern "C" int gh_profile_bytes(gh_t *h, int kernel, double *bytes_per_launch)
     return GH_OK;
 }
 
+// path rows a caller hands in ([n_paths][n1] symbol indices): the first cell that is none, reported under `code`
+static int check_symbol_rows(const uint8_t *paths, int n_paths, size_t n1, int code)
+{
+    const size_t path_bytes = (size_t)n_paths * n1;
+    uint8_t top = 0;
+    for (size_t q = 0; q < path_bytes; q++) top = std::max(top, paths[q]);
+    if (top > 6)
+        for (size_t q = 0; q < path_bytes; q++)
+            if (paths[q] > 6) return fail(code, "path %d holds %d at SNP %d: not a symbol index", (int)(q / n1), paths[q], (int)(q % n1));
+    return GH_OK;
+}
+
 // read assignment (gh_assign_reads) -----------------------------------------------------------
 #include "assign.hpp"
 // scoring given haplotypes (gh_score_paths) ---------------------------------------------------
 #include "score.hpp"
+// the chain table and the recovery loop the two decoders below share -----------------------------------
+#include "chain_table.hpp"
 // beam search over the chain likelihood (gh_beam_paths, gh_beam_spin, gh_beam_info) ------------------
 #include "beam.hpp"
 // exact decoding of the chain likelihood (gh_viterbi_path, gh_viterbi_spin, gh_viterbi_info) -----------

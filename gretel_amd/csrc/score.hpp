@@ -183,57 +183,38 @@ extern "C" int gh_score_paths(gh_t *h, const uint8_t *paths, int n_paths, gh_sco
     if (n_paths == 0) return GH_OK;
     const int N = h->N;
     const size_t n1 = (size_t)N + 1;
-    const size_t path_bytes = (size_t)n_paths * n1;
-    uint8_t top = 0;
-    for (size_t q = 0; q < path_bytes; q++) top = std::max(top, paths[q]);
-    if (top > 6)
-        for (size_t q = 0; q < path_bytes; q++)
-            if (paths[q] > 6) return fail(GH_ERR_SYMBOL, "path %d holds %d at SNP %d: not a symbol index", (int)(q / n1), paths[q], (int)(q % n1));
+    int rc = check_symbol_rows(paths, n_paths, n1, GH_ERR_SYMBOL);
+    if (rc) return rc;
     if (h->band_zero) return fail(GH_ERR_STATE, "gh_score_paths before any fill or import: the tensor holds no evidence");
     if (set_dev(h)) return GH_ERR_HIP;
-    int rc = ensure_marg(h);
-    if (rc) return rc;
+    if ((rc = ensure_marg(h))) return rc;
 
-    // one device block, kept on the handle: per slab its paths, records, weights, margins and picks
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    // one device block, kept on the handle: per slab its paths, records, weights, margins and picks (score_layout)
     const size_t per_path = n1 * (8 + 8 + 1 + 1);
     const int slab = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)n_paths, 65535), SCORE_SLAB_BYTES / per_path));
-    const size_t path_b = up((size_t)slab * n1), rec_b = up((size_t)slab * sizeof(gh_score_rec)), dbl_b = up((size_t)slab * n1 * 8);
-    const size_t need = 2 * path_b + rec_b + 2 * dbl_b;
-    if (need > h->score_cap) {
-        HIPCHK(hipStreamSynchronize(h->stream));
-        hipFree(h->score_buf);
-        h->score_buf = nullptr;
-        h->score_cap = 0;
-        HIPCHK(hipMalloc(&h->score_buf, need));
-        h->score_cap = need;
-    }
-    char *base = (char *)h->score_buf;
-    double *d_weight = (double *)base, *d_margin = (double *)(base + dbl_b);
-    gh_score_rec *d_recs = (gh_score_rec *)(base + 2 * dbl_b);
-    uint8_t *d_paths = (uint8_t *)(base + 2 * dbl_b + rec_b), *d_pick = d_paths + path_b;
+    if ((rc = scratch_reserve(h, &h->score, score_layout(nullptr, slab, n1).total, "gh_score_paths: the scratch of one slab of paths"))) return rc;
+    const score_bufs d = score_layout(h->score.buf, slab, n1);
 
-    // (the to-major copy while it mirrors the band: a column sum is then a contiguous run, same addends in the same order)
-    const void *tb = (h->tband && h->tband_epoch == h->band_epoch) ? h->tband : nullptr;
+    const void *tb = tband_current(h);
     const int orig_slot = h->have_orig ? 11 : 0;
     for (int q0 = 0; q0 < n_paths; q0 += slab) {
         const int k = std::min(slab, n_paths - q0);
         const size_t o = (size_t)q0 * n1, cells = (size_t)k * n1;
-        HIPCHK(hipMemcpyAsync(d_paths, paths + o, cells, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(d.paths, paths + o, cells, hipMemcpyHostToDevice, h->stream));
         with_storage(h, [&](auto z) {
             using T = decltype(z);
             hipLaunchKernelGGL(k_score_pos<T>, dim3((unsigned)((n1 + SCORE_POS_PER_BLOCK - 1) / SCORE_POS_PER_BLOCK), (unsigned)k),
                                dim3(SCORE_BLOCK), 0, h->stream, (const T *)h->band, (const T *)tb, N, h->W, h->cfg.cond_mode, h->L,
-                               h->cfg.marginal_term, h->cnt, h->marg, h->nvalid, h->cmask, h->sm, d_paths, d_weight, d_margin, d_pick);
+                               h->cfg.marginal_term, h->cnt, h->marg, h->nvalid, h->cmask, h->sm, d.paths, d.weight, d.margin, d.pick);
         });
-        { int rc_ = post_launch(h, "k_score_pos"); if (rc_) return rc_; }
-        hipLaunchKernelGGL(k_score_sum, dim3((unsigned)k, 3), dim3(64), 0, h->stream, d_weight, d_margin, d_pick, d_paths, h->cmask,
-                           h->marg, h->minfo, orig_slot, N, h->sm, d_recs);
-        { int rc_ = post_launch(h, "k_score_sum"); if (rc_) return rc_; }
-        HIPCHK(hipMemcpyAsync(recs + q0, d_recs, (size_t)k * sizeof(gh_score_rec), hipMemcpyDeviceToHost, h->stream));
-        if (weight) HIPCHK(hipMemcpyAsync(weight + o, d_weight, cells * 8, hipMemcpyDeviceToHost, h->stream));
-        if (margin) HIPCHK(hipMemcpyAsync(margin + o, d_margin, cells * 8, hipMemcpyDeviceToHost, h->stream));
-        if (pick) HIPCHK(hipMemcpyAsync(pick + o, d_pick, cells, hipMemcpyDeviceToHost, h->stream));
+        if ((rc = post_launch(h, "k_score_pos"))) return rc;
+        hipLaunchKernelGGL(k_score_sum, dim3((unsigned)k, 3), dim3(64), 0, h->stream, d.weight, d.margin, d.pick, d.paths, h->cmask,
+                           h->marg, h->minfo, orig_slot, N, h->sm, d.recs);
+        if ((rc = post_launch(h, "k_score_sum"))) return rc;
+        HIPCHK(hipMemcpyAsync(recs + q0, d.recs, (size_t)k * sizeof(gh_score_rec), hipMemcpyDeviceToHost, h->stream));
+        if (weight) HIPCHK(hipMemcpyAsync(weight + o, d.weight, cells * 8, hipMemcpyDeviceToHost, h->stream));
+        if (margin) HIPCHK(hipMemcpyAsync(margin + o, d.margin, cells * 8, hipMemcpyDeviceToHost, h->stream));
+        if (pick) HIPCHK(hipMemcpyAsync(pick + o, d.pick, cells, hipMemcpyDeviceToHost, h->stream));
         // (the next slab overwrites the block: its results have left, and the caller's path rows have been read, behind this)
         HIPCHK(hipStreamSynchronize(h->stream));
     }

@@ -1,0 +1,110 @@
+// scratch_layout.hpp -- how gh_assign_reads, gh_score_paths, the beam and the exact decoder lay out their device scratch blocks
+// (dev_scratch, gretel_hip.hip).  Host only, plain C++17, no HIP: tests/native/scratch_layout.cpp compiles it alone and checks
+// every layout below against its sizes written out by hand.  Each user lists its parts ONCE, in a *_layout function: called with
+// base = nullptr it sizes the block (`total`, every part null), called with the block it hands out the typed parts.  A struct's
+// members stand in the order of the block, and a braced list is evaluated left to right: the list IS the layout.
+// ---------------------------------------------------------------------------------------------
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+#include "gretel_hip.h"
+
+constexpr size_t scratch_up(size_t x) { return (x + 255) & ~(size_t)255; }      // every part starts on a 256-byte boundary
+
+struct scratch_carver {
+    char *base;            // nullptr: the sizing pass
+    size_t used = 0;
+    template <typename T> T *take(size_t count)
+    {
+        T *p = base ? reinterpret_cast<T *>(base + used) : nullptr;
+        used += scratch_up(count * sizeof(T));
+        return p;
+    }
+};
+
+// gh_assign_reads: counters [3][n_paths] with the totals [8] right behind them, the paths, the match masks [nw][N+1][5],
+// and where the caller wants them the per-read results [3][n_reads]
+struct assign_bufs {
+    unsigned long long *cnt;
+    uint8_t *paths;
+    unsigned long long *mask;
+    int32_t *read;
+    size_t total;
+};
+
+inline assign_bufs assign_layout(void *base, int n_paths, int N, int64_t n_reads, bool per_read)
+{
+    scratch_carver c{(char *)base};
+    const size_t n1 = (size_t)N + 1, nw = ((size_t)n_paths + 63) / 64;
+    return {c.take<unsigned long long>(3 * (size_t)n_paths + 8), c.take<uint8_t>((size_t)n_paths * n1), c.take<unsigned long long>(nw * n1 * 5),
+            per_read ? c.take<int32_t>((size_t)n_reads * 3) : nullptr, c.used};
+}
+
+// gh_score_paths: one slab's weights, margins, records, paths and picks
+struct score_bufs {
+    double *weight, *margin;
+    gh_score_rec *recs;
+    uint8_t *paths, *pick;
+    size_t total;
+};
+
+inline score_bufs score_layout(void *base, int slab, size_t n1)
+{
+    scratch_carver c{(char *)base};
+    const size_t cells = (size_t)slab * n1;
+    return {c.take<double>(cells), c.take<double>(cells), c.take<gh_score_rec>((size_t)slab), c.take<uint8_t>(cells), c.take<uint8_t>(cells), c.used};
+}
+
+// the beam: its chain table (`table_doubles` = N * beam_src_doubles(L)), a row of back-pointer bytes per position (whole words:
+// `bps` bytes), GH_BEAM_MAX path rows and scores, and what the walk leaves for the trace and the host
+struct beam_out {
+    int n_out, hole_at;
+    int end, rows;     // what k_beam_trace follows: `rows` hypotheses from position `end` down
+};
+
+struct beam_bufs {
+    double *Gb;
+    uint8_t *bp, *paths;
+    double *ll;
+    beam_out *out;
+    int bps;
+    size_t total;
+};
+
+inline beam_bufs beam_layout(void *base, int N, size_t table_doubles, int width)
+{
+    scratch_carver c{(char *)base};
+    const size_t n1 = (size_t)N + 1;
+    const int bps = (width + 3) & ~3;
+    return {c.take<double>(table_doubles), c.take<uint8_t>(n1 * bps), c.take<uint8_t>(n1 * GH_BEAM_MAX), c.take<double>(GH_BEAM_MAX),
+            c.take<beam_out>(1), bps, c.used};
+}
+
+// the exact decoder.  `out` is the FIRST part: vit_run reserves the block twice in one call -- `states` = 0 while only k_vit_union's
+// word is wanted, then in full once U has said how many states there are -- and finds `out` at offset 0 under both.
+struct vit_out {
+    uint32_t U;        // k_vit_union
+    int hole_at;       // k_vit_walk
+    int end_state;     // k_vit_trace
+    int pad;
+    double ll;         // k_vit_trace
+};
+
+struct vit_bufs {
+    vit_out *out;
+    double *Gb;
+    uint8_t *bp;           // [N + 1][states] and four bytes more: k_vit_trace copies whole words
+    double *vend;
+    uint8_t *okend, *path;
+    size_t total;
+};
+
+inline vit_bufs vit_layout(void *base, int N, size_t table_doubles, int states)
+{
+    scratch_carver c{(char *)base};
+    const size_t n1 = (size_t)N + 1, ns = (size_t)states;
+    vit_out *out = c.take<vit_out>(1);
+    if (!states) return {out, nullptr, nullptr, nullptr, nullptr, nullptr, c.used};
+    return {out, c.take<double>(table_doubles), c.take<uint8_t>(n1 * ns + 4), c.take<double>(ns), c.take<uint8_t>(ns), c.take<uint8_t>(n1), c.used};
+}

@@ -2,8 +2,8 @@
 // where the definition stands; INTEGRATION.md "Exact decoding").  An edge weight depends on the last Le = min(L, N) picks only, so
 // the maximum of gh_score_paths' ll_chain over ALL full paths is a dynamic programme over S^Le states, S = the candidate slots
 // the window offers anywhere.  fl(a + w) is monotone in a: keeping the best prefix per state loses nothing, the result is the
-// maximum bit for bit.  The tensor is only read; the table is beam.hpp's (k_beam_table, beam_src_doubles), in a scratch block of
-// the handle of its own.
+// maximum bit for bit.  The tensor is only read; the table is chain_table.hpp's (k_beam_table, beam_src_doubles), in a scratch
+// block of the handle of its own.
 //
 //   k_vit_union  U = the union of the candidate bits (compact indices b5) over p = 1..N.  A digit is a slot's rank within U; the
 //                compact order is the candidate order, so ascending digits are ascending q.
@@ -38,14 +38,6 @@
 static_assert(VIT_OWN * VIT_THREADS == GH_VITERBI_MAX_STATES && 5 * VIT_MAX_LE <= 64, "four states a thread; twelve masks a word");
 static_assert(2 * (size_t)GH_VITERBI_MAX_STATES * 8 + (VIT_MAX_LE + 1) * (size_t)beam_src_doubles(VIT_MAX_LE) * 8 <= BEAM_LDS_MAX,
               "two score rows and the ring of the longest state fit");
-
-struct vit_out {
-    uint32_t U;        // k_vit_union
-    int hole_at;       // k_vit_walk
-    int end_state;     // k_vit_trace
-    int pad;
-    double ll;         // k_vit_trace
-};
 
 __global__ void __launch_bounds__(256)
 k_vit_union(const double *__restrict__ minfo, int N, vit_out *__restrict__ out)
@@ -264,47 +256,18 @@ k_vit_trace(const uint8_t *__restrict__ bp, const double *__restrict__ vend, con
     }
 }
 
-// host ----------------------------------------------------------------------------------------
-struct vit_bufs {
-    double *Gb, *vend;
-    uint8_t *bp, *okend, *path;
-    vit_out *out;
-};
-
-static int vit_check(const gh_handle *h, const char *who)
-{
-    if (h->cfg.offer_zero)
-        return fail(GH_ERR_ARG, "%s: the handle offers zero-count candidates (offer_zero), whose weights can be NaN (-inf + +inf): no order ranks them", who);
-    if (h->band_zero) return fail(GH_ERR_STATE, "%s before any fill or import: the tensor holds no evidence", who);
-    return GH_OK;
-}
-
-static int vit_grow(gh_handle *h, size_t need)
-{
-    if (need <= h->vit_cap) return GH_OK;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    hipFree(h->vit_buf);
-    h->vit_buf = nullptr;
-    h->vit_cap = 0;
-    if (hipMalloc(&h->vit_buf, need) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(GH_ERR_NOMEM, "the exact decoder's scratch (%zu bytes: the table grows with N * L, the back-pointers with N * states) cannot be had", need);
-    }
-    h->vit_cap = need;
-    return GH_OK;
-}
+// host ---------------------------------------------------------------------------------------- (vit_out, vit_bufs: scratch_layout.hpp)
+static const char VIT_SCRATCH[] = "the exact decoder's scratch, whose table grows with N * L and whose back-pointers with N * states,";
 
 // one exact decoding of the tensor as it stands: the results stay in the handle's scratch (`b`), *ho = hole, score and U
 static int vit_run(gh_handle *h, vit_bufs *b, vit_out *ho, const char *who)
 {
-    const int N = h->N;
-    const int L = h->L < N ? h->L : N;                        // (lags beyond the window's first position are never summed)
-    int rc = ensure_marg(h);
+    const int N = h->N, L = chain_lags(h);
+    int rc = ensure_marg(h);                                    // (k_vit_union reads minfo)
     if (rc) return rc;
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     // U first: it decides whether the decoder serves this window at all
-    if ((rc = vit_grow(h, up(sizeof(vit_out))))) return rc;
-    vit_out *d_out = (vit_out *)h->vit_buf;
+    if ((rc = scratch_reserve(h, &h->vit, vit_layout(nullptr, N, 0, 0).total, VIT_SCRATCH))) return rc;
+    vit_out *d_out = vit_layout(h->vit.buf, N, 0, 0).out;
     hipLaunchKernelGGL(k_vit_union, dim3(1), dim3(256), 0, h->stream, (const double *)h->minfo, N, d_out);
     if ((rc = post_launch(h, "k_vit_union"))) return rc;
     HIPCHK(hipMemcpyAsync(ho, d_out, sizeof *ho, hipMemcpyDeviceToHost, h->stream));
@@ -313,7 +276,7 @@ static int vit_run(gh_handle *h, vit_bufs *b, vit_out *ho, const char *who)
     const int S = __builtin_popcount(U);
     if (S == 0) {                                             // nothing offered anywhere: the hole is the first position
         ho->hole_at = 1;
-        h->vit_last[0] = 0; h->vit_last[1] = L; h->vit_last[2] = 0; h->vit_last[3] = (int64_t)h->vit_cap;
+        h->vit_last[0] = 0; h->vit_last[1] = L; h->vit_last[2] = 0; h->vit_last[3] = (int64_t)h->vit.cap;
         return GH_OK;
     }
     long long states = 1;
@@ -326,28 +289,11 @@ static int vit_run(gh_handle *h, vit_bufs *b, vit_out *ho, const char *who)
                     "holds on chip: lower L, or use the beam (--beam, gh_beam_paths)", who, S, L, cnt, GH_VITERBI_MAX_STATES);
     }
     const int ns = (int)states;
-    const size_t n1 = (size_t)N + 1;
-    const size_t out_b = up(sizeof(vit_out)), gb_b = up((size_t)N * beam_src_doubles(L) * 8), bp_b = up(n1 * ns + 4);
-    const size_t ve_b = up((size_t)ns * 8), ok_b = up((size_t)ns), path_b = up(n1);
-    const size_t need = out_b + gb_b + bp_b + ve_b + ok_b + path_b;
-    if ((rc = vit_grow(h, need))) return rc;
-    char *base = (char *)h->vit_buf;
-    b->out = (vit_out *)base;
-    b->Gb = (double *)(base + out_b);
-    b->bp = (uint8_t *)(base + out_b + gb_b);
-    b->vend = (double *)(base + out_b + gb_b + bp_b);
-    b->okend = (uint8_t *)(base + out_b + gb_b + bp_b + ve_b);
-    b->path = b->okend + ok_b;
-
-    const void *tb = (h->tband && h->tband_epoch == h->band_epoch) ? h->tband : nullptr;
-    const size_t total = (size_t)N * beam_src_doubles(L);
-    const unsigned nb = (unsigned)std::min<size_t>((total + 255) / 256, 256 * 16);
-    with_storage(h, [&](auto z) {
-        using T = decltype(z);
-        hipLaunchKernelGGL(k_beam_table<T>, dim3(nb), dim3(256), 0, h->stream, (const T *)h->band, (const T *)tb, N, h->W, L, h->cfg.cond_mode,
-                           h->cnt, h->nvalid, h->cmask, h->minfo, h->sm, b->Gb);
-    });
-    if ((rc = post_launch(h, "k_beam_table"))) return rc;
+    const size_t table_doubles = (size_t)N * beam_src_doubles(L);
+    const size_t need = vit_layout(nullptr, N, table_doubles, ns).total;
+    if ((rc = scratch_reserve(h, &h->vit, need, VIT_SCRATCH))) return rc;
+    *b = vit_layout(h->vit.buf, N, table_doubles, ns);
+    if ((rc = chain_table_build(h, L, b->Gb))) return rc;
 
     static const bool no_stage = env_off("GH_VIT_STAGE");       // (A/B: the table blocks from global memory)
     const size_t rows = 2 * (size_t)ns * 8;
@@ -371,17 +317,14 @@ static int vit_run(gh_handle *h, vit_bufs *b, vit_out *ho, const char *who)
     if ((rc = post_launch(h, "k_vit_trace"))) return rc;
     HIPCHK(hipMemcpyAsync(ho, b->out, sizeof *ho, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->vit_last[0] = S;
-    h->vit_last[1] = L;
-    h->vit_last[2] = ns;
-    h->vit_last[3] = (int64_t)need;
+    h->vit_last[0] = S; h->vit_last[1] = L; h->vit_last[2] = ns; h->vit_last[3] = (int64_t)need;
     return GH_OK;
 }
 
 extern "C" int gh_viterbi_path(gh_t *h, uint8_t *path_out, double *ll_chain, int *hole_at)
 {
     if (!h || !path_out || !ll_chain || !hole_at) return fail(GH_ERR_ARG, "null argument");
-    int rc = vit_check(h, "gh_viterbi_path");
+    int rc = decode_check(h, "gh_viterbi_path");
     if (rc) return rc;
     if (set_dev(h)) return GH_ERR_HIP;
     vit_bufs b;
@@ -400,34 +343,18 @@ extern "C" int gh_viterbi_spin(gh_t *h, int max_paths, double min_remove, uint8_
 {
     if (!h || !paths_out || !recs || !n_out || !hole_at) return fail(GH_ERR_ARG, "null argument");
     if (max_paths < 0) return fail(GH_ERR_ARG, "max_paths < 0");
-    int rc = vit_check(h, "gh_viterbi_spin");
+    int rc = decode_check(h, "gh_viterbi_spin");
     if (rc) return rc;
     if (set_dev(h)) return GH_ERR_HIP;
-    *n_out = 0; *hole_at = 0;
-    if (max_paths == 0) return GH_OK;
-    if (!h->have_orig && (rc = gh_snapshot_original(h))) return rc;
-    const size_t n1 = (size_t)h->N + 1;
-    for (int s = 0; s < max_paths; s++) {
+    return decode_spin(h, max_paths, min_remove, paths_out, recs, ll_chain, n_out, hole_at, [&](decoded *d) -> int {
         vit_bufs b;
         vit_out ho;
         if ((rc = vit_run(h, &b, &ho, "gh_viterbi_spin"))) return rc;
-        if (ho.hole_at) { *hole_at = ho.hole_at; break; }
-        uint8_t *path = paths_out + n1 * s;
-        HIPCHK(hipMemcpyAsync(path, b.path, n1, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        // the record of that path on the tensor as it stands (hp_original under the snapshot), then the reweight
-        gh_score_rec sr;
-        if ((rc = gh_score_paths(h, path, 1, &sr, nullptr, nullptr, nullptr))) return rc;
-        gh_path_rec &r = recs[s];
-        r.hp_current = sr.hp_current;
-        r.hp_original = sr.hp_original;
-        r.min_marginal = sr.min_marginal;
-        r.ratio = sr.min_marginal < min_remove ? min_remove : sr.min_marginal;
-        if ((rc = gh_reweight_path(h, path, r.ratio, &r.magnitude))) return rc;
-        if (ll_chain) ll_chain[s] = ho.ll;
-        *n_out = s + 1;
-    }
-    return GH_OK;
+        d->hole = ho.hole_at;
+        d->d_path = b.path;
+        d->ll = ho.ll;                                          // (it came home with vit_out)
+        return GH_OK;
+    });
 }
 
 extern "C" int gh_viterbi_info(const gh_t *h, int64_t out[4])

@@ -371,14 +371,17 @@ class Hansel:
     def beam_spin(self, width, max_paths=100, min_remove=0.01):
         """gretel/cmd.py:148-179 with the rank-0 path of a beam of `width` in place of generate_path (gh_beam_spin: a host loop,
         not the throughput path).  Returns spin()'s dict plus ll_chain float64[n], the beam score of every path."""
+        return self._decode_spin(self._lib.gh_beam_spin, int(width), max_paths=max_paths, min_remove=min_remove)
+
+    def _decode_spin(self, fn, *lead_args, max_paths, min_remove):
+        """A decoder's recovery loop in the library (gh_beam_spin, gh_viterbi_spin: `lead_args` between the handle and max_paths)."""
         self._ensure()
         nrec = C.sizeof(_lib.gh_path_rec) // 8
         paths = np.empty((max(0, max_paths), self.n + 1), dtype=np.uint8)
         recs = np.empty((max(1, max_paths), nrec), dtype=np.float64)
         ll = np.zeros(max(1, max_paths))
         n, hole = C.c_int(), C.c_int()
-        check(self._lib.gh_beam_spin(self._h, int(width), int(max_paths), float(min_remove), _p(paths), _p(recs), _p(ll),
-                                     C.byref(n), C.byref(hole)))
+        check(fn(self._h, *lead_args, int(max_paths), float(min_remove), _p(paths), _p(recs), _p(ll), C.byref(n), C.byref(hole)))
         k = n.value
         if k:
             self.is_weighted = True
@@ -386,13 +389,16 @@ class Hansel:
         return dict(n=k, hole_at=hole.value, paths=paths[:k], hp_current=r[:, 0].copy(), hp_original=r[:, 1].copy(),
                     ratio=r[:, 2].copy(), magnitude=r[:, 3].copy(), min_marginal=r[:, 4].copy(), ll_chain=ll[:k].copy())
 
+    def _info4(self, fn):
+        self._ensure()
+        out = np.zeros(4, dtype=np.int64)
+        check(fn(self._h, _p(out)))
+        return tuple(int(v) for v in out)
+
     def beam_info(self):
         """The last beam run on this handle (gh_beam_info): (1 if the table slice was staged through LDS, source positions the
         LDS ring holds, threads of the walk workgroup, bytes of the beam's device scratch)."""
-        self._ensure()
-        out = np.zeros(4, dtype=np.int64)
-        check(self._lib.gh_beam_info(self._h, _p(out)))
-        return tuple(int(v) for v in out)
+        return self._info4(self._lib.gh_beam_info)
 
     def viterbi_path(self):
         """The full path of largest chain likelihood on the tensor as it is now, exactly (gh_viterbi_path; the definition and
@@ -410,28 +416,12 @@ class Hansel:
     def viterbi_spin(self, max_paths=100, min_remove=0.01):
         """gretel/cmd.py:148-179 with the exact path in place of generate_path (gh_viterbi_spin: a host loop, not the
         throughput path).  Returns beam_spin()'s dict: ll_chain float64[n] is the exact maximum when each path was found."""
-        self._ensure()
-        nrec = C.sizeof(_lib.gh_path_rec) // 8
-        paths = np.empty((max(0, max_paths), self.n + 1), dtype=np.uint8)
-        recs = np.empty((max(1, max_paths), nrec), dtype=np.float64)
-        ll = np.zeros(max(1, max_paths))
-        n, hole = C.c_int(), C.c_int()
-        check(self._lib.gh_viterbi_spin(self._h, int(max_paths), float(min_remove), _p(paths), _p(recs), _p(ll),
-                                        C.byref(n), C.byref(hole)))
-        k = n.value
-        if k:
-            self.is_weighted = True
-        r = recs[:k]
-        return dict(n=k, hole_at=hole.value, paths=paths[:k], hp_current=r[:, 0].copy(), hp_original=r[:, 1].copy(),
-                    ratio=r[:, 2].copy(), magnitude=r[:, 3].copy(), min_marginal=r[:, 4].copy(), ll_chain=ll[:k].copy())
+        return self._decode_spin(self._lib.gh_viterbi_spin, max_paths=max_paths, min_remove=min_remove)
 
     def viterbi_info(self):
         """The last exact decoding on this handle (gh_viterbi_info): (S candidate symbols, Le = min(L, N), states = S^Le,
         bytes of the decoder's device scratch)."""
-        self._ensure()
-        out = np.zeros(4, dtype=np.int64)
-        check(self._lib.gh_viterbi_info(self._h, _p(out)))
-        return tuple(int(v) for v in out)
+        return self._info4(self._lib.gh_viterbi_info)
 
     def clear(self):
         self._staged = []

@@ -230,7 +230,8 @@ int gh_panel_spin(gh_batch_t *b, int max_paths, double min_remove, uint8_t *path
  * |T| > 1: ambiguous (-2, shared[h] += 1 for every h in T); else unique (hap = h, unique[h] += 1, mismatches[h] += I - best).
  * unique / shared / mismatches: [n_paths]; read_hap / read_best / read_informative: [n_reads] each, each may be NULL.
  * GH_ERR_ARG for n_paths < 0, min_snps < 1, max_mismatch < -1, a path byte above 6, or reads on another device than h;
- * GH_ERR_SYMBOL when a read holds a byte outside "ACGTN-_".  Reads the table and the paths only: the tensor, L, the fill
+ * GH_ERR_SYMBOL when a read holds a byte outside "ACGTN-_"; GH_ERR_NOMEM when the device scratch cannot be had (the message
+ * names its size).  Reads the table and the paths only: the tensor, L, the fill
  * statistics and the snapshot stay as they are.  All integers: the results do not depend on the order of the device's atomics. */
 typedef struct {
     int64_t n_reads;        /* reads in the table */
@@ -262,7 +263,8 @@ int gh_assign_reads(gh_t *h, const gh_reads_t *reads, const uint8_t *paths, int 
  * its hp_current, hp_original and min_marginal bit for bit.
  * recs: [n_paths]; weight / margin / pick: [n_paths][N + 1], each may be NULL; pick[.][0] = 6, weight[.][0] = margin[.][0] = 0.
  * GH_ERR_ARG for a null h, paths or recs or n_paths < 0; n_paths == 0 returns GH_OK and writes nothing; GH_ERR_SYMBOL for a path
- * byte above 6; GH_ERR_STATE before any fill, add or import.  Reads the tensor only: the band, L, the fill statistics, the
+ * byte above 6; GH_ERR_STATE before any fill, add or import; GH_ERR_NOMEM when the device scratch cannot be had (the message
+ * names its size).  Reads the tensor only: the band, L, the fill statistics, the
  * snapshot and the results of a following gh_spin stay as they are.  The device scratch is bounded whatever n_paths is (the paths
  * go through in slabs). */
 typedef struct {

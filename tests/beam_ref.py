@@ -44,32 +44,8 @@ def beam_spin(o, n, width, max_paths, min_remove=0.01, cand_order="ACGT-", origi
     """gretel/cmd.py:148-179 with the beam's rank-0 path in place of generate_path: Hansel.beam_spin's dict as arrays.
     original: the marginals the handle's snapshot froze (score_ref.marginals at that moment); None = no snapshot yet, it is
     taken here, as gh_beam_spin takes it."""
-    if original is None:
-        original = score_ref.marginals(o, n)
-    out = dict(paths=[], hp_current=[], hp_original=[], ratio=[], magnitude=[], min_marginal=[], ll_chain=[])
-    hole_at = 0
-    for _ in range(max_paths):
+    def decode():
         res = beam(o, n, width, cand_order)
-        if res["hole_at"]:
-            hole_at = res["hole_at"]
-            break
-        x = res["paths"][0]
-        hc = ho = 0.0
-        mn = float("inf")
-        for p in range(1, n + 1):
-            m = o.marginal(int(x[p]), p)
-            mn = min(mn, m)
-            hc += score_ref.log10(m)
-            ho += score_ref.log10(original[p][int(x[p])])
-        ratio = max(mn, min_remove)
-        out["paths"].append(x)
-        out["hp_current"].append(hc)
-        out["hp_original"].append(ho)
-        out["min_marginal"].append(mn)
-        out["ratio"].append(ratio)
-        out["magnitude"].append(o.reweight_path(x, ratio))
-        out["ll_chain"].append(res["ll_chain"][0])
-    k = len(out["paths"])
-    res = {key: np.array(v, dtype=np.float64) for key, v in out.items() if key != "paths"}
-    res.update(n=k, hole_at=hole_at, paths=np.array(out["paths"], dtype=np.uint8).reshape(k, n + 1))
-    return res
+        return (res["hole_at"], None, None) if res["hole_at"] else (0, res["paths"][0], res["ll_chain"][0])
+
+    return score_ref.recover_spin(o, n, max_paths, min_remove, original, decode)

@@ -90,6 +90,39 @@ def score(o, paths, n, cand_order="ACGT-", original=None):
     return out
 
 
+def recover_spin(o, n, max_paths, min_remove, original, decode):
+    """gretel/cmd.py:148-179 around any decoder: decode() -> (hole_at, path, ll) on `o` as it stands, the path then recorded and
+    reweighted.  Hansel.beam_spin's / viterbi_spin's dict as arrays.  original: the marginals the handle's snapshot froze
+    (marginals() at that moment); None = no snapshot yet, it is taken here."""
+    if original is None:
+        original = marginals(o, n)
+    out = dict(paths=[], hp_current=[], hp_original=[], ratio=[], magnitude=[], min_marginal=[], ll_chain=[])
+    hole_at = 0
+    for _ in range(max_paths):
+        hole_at, x, ll = decode()
+        if hole_at:
+            break
+        hc = ho = 0.0
+        mn = float("inf")
+        for p in range(1, n + 1):
+            m = o.marginal(int(x[p]), p)
+            mn = min(mn, m)
+            hc += log10(m)
+            ho += log10(original[p][int(x[p])])
+        ratio = max(mn, min_remove)
+        out["paths"].append(x)
+        out["hp_current"].append(hc)
+        out["hp_original"].append(ho)
+        out["min_marginal"].append(mn)
+        out["ratio"].append(ratio)
+        out["magnitude"].append(o.reweight_path(x, ratio))
+        out["ll_chain"].append(ll)
+    k = len(out["paths"])
+    res = {key: np.array(v, dtype=np.float64) for key, v in out.items() if key != "paths"}
+    res.update(n=k, hole_at=hole_at, paths=np.array(out["paths"], dtype=np.uint8).reshape(k, n + 1))
+    return res
+
+
 def _nan_named(v):
     """== on lists takes an infinity as equal to itself but not a NaN: name the NaNs, so that a NaN must meet a NaN."""
     if isinstance(v, list):

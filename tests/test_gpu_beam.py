@@ -3,7 +3,6 @@ beam_info; --beam of gretel_amd.cmd) against the plain statement of the definiti
 and scores are compared exactly -- the order of every addition and every comparison is fixed; only the removed mass of a reweight
 goes through spec_util.same's relative 1e-10, as everywhere."""
 import ctypes as C
-import functools
 import io
 import os
 import types
@@ -12,48 +11,13 @@ import numpy as np
 import pytest
 
 import beam_ref
-from conftest import REFDATA
-from gretel_amd import _lib, cmd, util
+from decode_util import BAM, E_MT, SYMS, VCF, _cli_oracle, _from_haps, _same_spin, _table
+from gretel_amd import _lib, cmd
 from gretel_amd.hansel import Hansel
-from gretel_amd.synth import make_config, make_support_table, sprinkle_deletions
-from oracle.c_oracle import COracle
+from gretel_amd.synth import make_support_table
 from spec_util import make_pair, same, spec_id
 
 pytestmark = pytest.mark.gpu
-BAM = os.path.join(REFDATA, "test.bam")
-VCF = os.path.join(REFDATA, "test.vcf.gz")
-SYMS = "ACGTN-_"
-E_MT = dict(cond_mode="E", marginal_term=True)
-
-
-@functools.lru_cache(maxsize=None)
-def _table(which):
-    if which == "a":
-        t = make_support_table(60, 800, k=None, seed=5)
-        sprinkle_deletions(t, 0.05, seed=6)
-    elif which == "b":                                       # the 300-SNP table of tests/test_gpu_score.py
-        t = make_support_table(300, 6000, k=None, seed=31)
-        sprinkle_deletions(t, 0.05, seed=32)
-    else:
-        t = make_config("C2", seed=6)
-    return t
-
-
-def _from_haps(haps, band, L, skip=(), **kw):
-    """A device Hansel and the C oracle built cell by cell from whole haplotypes: every pair (i, i + d), d <= band, of
-    '_' + hap + '_' except the cells (i, i + 1) with i in `skip` -- position i then has no candidate."""
-    n = len(haps[0])
-    h = Hansel(n, band=band, **kw)
-    o = COracle(n, band, **kw)
-    for hap in haps:
-        full = "_" + hap + "_"
-        for i in range(n + 1):
-            for d in range(1, band + 1):
-                if i + d <= n + 1 and not (d == 1 and i in skip):
-                    h.add_observation(full[i], full[i + d], i, i + d)
-                    o.add(SYMS.index(full[i]), SYMS.index(full[i + d]), i, i + d)
-    h.L = o.L = L
-    return h, o
 
 
 def _check(h, o, width):
@@ -169,12 +133,6 @@ def test_mid_recovery_and_nothing_disturbed():
     assert np.array_equal(h.export_band(), o.export_band())
 
 
-def _same_spin(res, ref):
-    same(res, ref)
-    assert res["ll_chain"].tolist() == ref["ll_chain"].tolist()
-    assert res["min_marginal"].tolist() == ref["min_marginal"].tolist()
-
-
 @pytest.mark.parametrize("kw", [{}, E_MT], ids=spec_id)
 def test_beam_spin_width_8(kw):
     t = _table("a")
@@ -257,13 +215,7 @@ def test_cli_beam_8_against_the_reference(tmp_path, capsys):
     want.mkdir()
     assert cmd.main([BAM, VCF, "hoot", "-s", "1", "-e", "20", "-p", "12", "-o", str(out), "--beam", "8", "--score-paths"]) == 0
     capsys.readouterr()
-    v = util.process_vcf(VCF, "hoot", 1, 20)
-    n = v["N"]
-    h = util.load_from_bam(BAM, "hoot", 1, 20, v)
-    rank, off, bases = util.support_table_from_bam(BAM, "hoot", 1, 20, v)
-    o = COracle(n, h.band)
-    o.fill(types.SimpleNamespace(rank=rank, off=off, bases=bases))
-    o.L = h.L
+    v, n, h, o = _cli_oracle()
     ref = beam_ref.beam_spin(o, n, 8, 12, cmd.MIN_REMOVE)
     capsys.readouterr()
     paths = cmd.paths_of_spin(h, ref, log=io.StringIO())

@@ -3,10 +3,8 @@ viterbi_spin / viterbi_info; --exact of gretel_amd.cmd) against the plain statem
 the C oracle).  Paths and scores are compared exactly -- the order of every addition and every comparison is fixed; only the
 removed mass of a reweight goes through spec_util.same's relative 1e-10, as everywhere."""
 import ctypes as C
-import functools
 import io
 import itertools
-import os
 import types
 
 import numpy as np
@@ -14,51 +12,13 @@ import pytest
 
 import score_ref
 import viterbi_ref
-from conftest import REFDATA
-from gretel_amd import _lib, cmd, util
+from decode_util import BAM, E_MT, SYMS, VCF, _cli_oracle, _from_haps, _same_spin, _table
+from gretel_amd import _lib, cmd
 from gretel_amd.hansel import Hansel
-from gretel_amd.synth import make_config, make_support_table, sprinkle_deletions
-from oracle.c_oracle import COracle
 from spec_util import make_pair, same, spec_id
 
 pytestmark = pytest.mark.gpu
-BAM = os.path.join(REFDATA, "test.bam")
-VCF = os.path.join(REFDATA, "test.vcf.gz")
-SYMS = "ACGTN-_"
-E_MT = dict(cond_mode="E", marginal_term=True)
 CAP = _lib.GH_VITERBI_MAX_STATES
-
-
-@functools.lru_cache(maxsize=None)
-def _table(which):
-    if which == "a":                                         # 60 SNPs, deletion columns: S = 5
-        t = make_support_table(60, 800, k=None, seed=5)
-        sprinkle_deletions(t, 0.05, seed=6)
-    elif which == "a4":                                      # the same reads without the deletions: S = 4
-        t = make_support_table(60, 800, k=None, seed=5)
-    elif which == "b":                                       # the 300-SNP table of tests/test_gpu_score.py
-        t = make_support_table(300, 6000, k=None, seed=31)
-        sprinkle_deletions(t, 0.05, seed=32)
-    else:
-        t = make_config("C2", seed=6)
-    return t
-
-
-def _from_haps(haps, band, L, skip=(), **kw):
-    """A device Hansel and the C oracle built cell by cell from whole haplotypes: every pair (i, i + d), d <= band, of
-    '_' + hap + '_' except the cells (i, i + 1) with i in `skip` -- position i then has no candidate."""
-    n = len(haps[0])
-    h = Hansel(n, band=band, **kw)
-    o = COracle(n, band, **kw)
-    for hap in haps:
-        full = "_" + hap + "_"
-        for i in range(n + 1):
-            for d in range(1, band + 1):
-                if i + d <= n + 1 and not (d == 1 and i in skip):
-                    h.add_observation(full[i], full[i + d], i, i + d)
-                    o.add(SYMS.index(full[i]), SYMS.index(full[i + d]), i, i + d)
-    h.L = o.L = L
-    return h, o
 
 
 def _str(path):
@@ -259,12 +219,6 @@ def test_refusals():
     assert L.gh_viterbi_info(None, info.ctypes.data) == _lib.GH_ERR_ARG
 
 
-def _same_spin(res, ref):
-    same(res, ref)
-    assert res["ll_chain"].tolist() == ref["ll_chain"].tolist()
-    assert res["min_marginal"].tolist() == ref["min_marginal"].tolist()
-
-
 @pytest.mark.parametrize("snapshot", [False, True], ids=["no-snapshot", "snapshot-before"])
 @pytest.mark.parametrize("kw", [{}, E_MT], ids=spec_id)
 def test_viterbi_spin(kw, snapshot):
@@ -289,13 +243,7 @@ def test_cli_exact(tmp_path, capsys):
     want.mkdir()
     assert cmd.main([BAM, VCF, "hoot", "-s", "1", "-e", "20", "-p", "12", "-o", str(out), "--exact", "--score-paths"]) == 0
     capsys.readouterr()
-    v = util.process_vcf(VCF, "hoot", 1, 20)
-    n = v["N"]
-    h = util.load_from_bam(BAM, "hoot", 1, 20, v)
-    rank, off, bases = util.support_table_from_bam(BAM, "hoot", 1, 20, v)
-    o = COracle(n, h.band)
-    o.fill(types.SimpleNamespace(rank=rank, off=off, bases=bases))
-    o.L = h.L
+    v, n, h, o = _cli_oracle()
     ref = viterbi_ref.viterbi_spin(o, n, 12, cmd.MIN_REMOVE)
     unweighted = h.copy()
     res = h.viterbi_spin(12, cmd.MIN_REMOVE)                 # a handle filled the same way

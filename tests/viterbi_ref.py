@@ -63,32 +63,8 @@ def viterbi_spin(o, n, max_paths, min_remove=0.01, cand_order="ACGT-", original=
     """gretel/cmd.py:148-179 with the exact path in place of generate_path: Hansel.viterbi_spin's dict as arrays.
     original: the marginals the handle's snapshot froze (score_ref.marginals at that moment); None = no snapshot yet, it is
     taken here, as gh_viterbi_spin takes it."""
-    if original is None:
-        original = score_ref.marginals(o, n)
-    out = dict(paths=[], hp_current=[], hp_original=[], ratio=[], magnitude=[], min_marginal=[], ll_chain=[])
-    hole_at = 0
-    for _ in range(max_paths):
+    def decode():
         res = viterbi(o, n, cand_order)
-        if res["hole_at"]:
-            hole_at = res["hole_at"]
-            break
-        x = res["path"]
-        hc = ho = 0.0
-        mn = float("inf")
-        for p in range(1, n + 1):
-            m = o.marginal(int(x[p]), p)
-            mn = min(mn, m)
-            hc += score_ref.log10(m)
-            ho += score_ref.log10(original[p][int(x[p])])
-        ratio = max(mn, min_remove)
-        out["paths"].append(x)
-        out["hp_current"].append(hc)
-        out["hp_original"].append(ho)
-        out["min_marginal"].append(mn)
-        out["ratio"].append(ratio)
-        out["magnitude"].append(o.reweight_path(x, ratio))
-        out["ll_chain"].append(res["ll_chain"])
-    k = len(out["paths"])
-    res = {key: np.array(v, dtype=np.float64) for key, v in out.items() if key != "paths"}
-    res.update(n=k, hole_at=hole_at, paths=np.array(out["paths"], dtype=np.uint8).reshape(k, n + 1))
-    return res
+        return res["hole_at"], res["path"], res["ll_chain"]
+
+    return score_ref.recover_spin(o, n, max_paths, min_remove, original, decode)
