@@ -161,6 +161,10 @@ def load():
         "gh_viterbi_path": [vp, vp, P(dbl), P(i32)],
         "gh_viterbi_spin": [vp, i32, dbl, vp, vp, vp, P(i32), P(i32)],
         "gh_viterbi_info": [vp, vp],
+        "gh_viterbi_states": [vp, vp],
+        "gh_panel_viterbi_spin": [vp, i32, dbl, vp, vp, vp, vp, vp, vp],
+        "gh_panel_viterbi_info": [vp, vp],
+        "gh_debug_panel_viterbi_phases": [i32, vp],
         "gh_coverage_sites": [i32, vp, vp, vp, i64, C.c_int32, C.c_int32, C.c_int32, vp, vp],
     }
     for name, args in sigs.items():

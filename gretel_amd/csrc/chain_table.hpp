@@ -85,6 +85,20 @@ struct decoded {
     double ll;                 // ... has brought it home already
 };
 
+// One recovered path's record and reweight, the same for every decoder and for gh_panel_viterbi_spin's windows: the record of
+// `path` on the tensor as it stands (gh_score_paths: hp_original under the snapshot), the ratio, then the reweight.
+static int decode_record(gh_handle *h, const uint8_t *path, double min_remove, gh_path_rec *r)
+{
+    int rc;
+    gh_score_rec sr;
+    if ((rc = gh_score_paths(h, path, 1, &sr, nullptr, nullptr, nullptr))) return rc;
+    r->hp_current = sr.hp_current;
+    r->hp_original = sr.hp_original;
+    r->min_marginal = sr.min_marginal;
+    r->ratio = sr.min_marginal < min_remove ? min_remove : sr.min_marginal;
+    return gh_reweight_path(h, path, r->ratio, &r->magnitude);
+}
+
 template <typename F>
 static int decode_spin(gh_handle *h, int max_paths, double min_remove, uint8_t *paths_out, gh_path_rec *recs, double *ll_chain,
                        int *n_out, int *hole_at, F &&decode_one)
@@ -102,15 +116,7 @@ static int decode_spin(gh_handle *h, int max_paths, double min_remove, uint8_t *
         HIPCHK(hipMemcpyAsync(path, d.d_path, n1, hipMemcpyDeviceToHost, h->stream));
         if (d.d_ll) HIPCHK(hipMemcpyAsync(&d.ll, d.d_ll, 8, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
-        // the record of that path on the tensor as it stands (hp_original under the snapshot), then the reweight
-        gh_score_rec sr;
-        if ((rc = gh_score_paths(h, path, 1, &sr, nullptr, nullptr, nullptr))) return rc;
-        gh_path_rec &r = recs[s];
-        r.hp_current = sr.hp_current;
-        r.hp_original = sr.hp_original;
-        r.min_marginal = sr.min_marginal;
-        r.ratio = sr.min_marginal < min_remove ? min_remove : sr.min_marginal;
-        if ((rc = gh_reweight_path(h, path, r.ratio, &r.magnitude))) return rc;
+        if ((rc = decode_record(h, path, min_remove, &recs[s]))) return rc;
         if (ll_chain) ll_chain[s] = d.ll;
         *n_out = s + 1;
     }

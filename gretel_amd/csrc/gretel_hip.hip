@@ -2411,6 +2411,11 @@ struct gh_batch {
     // d_wd holds 2n descriptors: every window's, and the lists the pipeline's launches take
     // panels (gh_panel_*): windows that differ in N, W and L.  N, W above are then the largest window's
     bool panel;
+    // gh_panel_viterbi_spin (viterbi_panel.hpp): descriptors, gathered vit_outs and path rows; an event per window that orders
+    // its handle's stream before the batch's; what gh_panel_viterbi_info reports
+    dev_scratch vit;
+    std::vector<hipEvent_t> vit_ev;
+    int64_t vit_info[4];
 };
 
 extern "C" int gh_batch_destroy(gh_batch_t *b)
@@ -2418,7 +2423,8 @@ extern "C" int gh_batch_destroy(gh_batch_t *b)
     if (!b) return GH_OK;
     hipSetDevice(b->dev);
     if (b->stream) hipStreamSynchronize(b->stream);
-    hipFree(b->d_wd); hipFree(b->d_states); hipFree(b->d_paths); hipFree(b->d_recs); hipFree(b->d_partial);
+    hipFree(b->d_wd); hipFree(b->d_states); hipFree(b->d_paths); hipFree(b->d_recs); hipFree(b->d_partial); hipFree(b->vit.buf);
+    for (hipEvent_t e : b->vit_ev) hipEventDestroy(e);
     for (int g = 0; g < 3; g++) {
         if (b->gstream[g]) { hipStreamSynchronize(b->gstream[g]); hipStreamDestroy(b->gstream[g]); }
         if (b->gevent[g]) hipEventDestroy(b->gevent[g]);
@@ -3441,3 +3447,5 @@ static int check_symbol_rows(const uint8_t *paths, int n_paths, size_t n1, int c
 #include "beam.hpp"
 // exact decoding of the chain likelihood (gh_viterbi_path, gh_viterbi_spin, gh_viterbi_info) -----------
 #include "viterbi.hpp"
+// ... over every window of a batch or panel, the decoders of a round side by side: gh_panel_viterbi_spin, gh_viterbi_states
+#include "viterbi_panel.hpp"

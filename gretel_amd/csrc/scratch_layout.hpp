@@ -108,3 +108,19 @@ inline vit_bufs vit_layout(void *base, int N, size_t table_doubles, int states)
     if (!states) return {out, nullptr, nullptr, nullptr, nullptr, nullptr, c.used};
     return {out, c.take<double>(table_doubles), c.take<uint8_t>(n1 * ns + 4), c.take<double>(ns), c.take<uint8_t>(ns), c.take<uint8_t>(n1), c.used};
 }
+
+// the exact decoder over a panel (viterbi_panel.hpp), a block of the batch: one descriptor per window (WD = vit_win, which holds
+// device types and so stands in viterbi_panel.hpp), the windows' vit_outs gathered for one copy to the host, and their path rows
+// gathered back to back (`path_bytes` = the sum of N_w + 1)
+template <typename WD> struct vit_panel_bufs {
+    WD *wd;
+    vit_out *outs;
+    uint8_t *paths;
+    size_t total;
+};
+
+template <typename WD> inline vit_panel_bufs<WD> vit_panel_layout(void *base, int n, size_t path_bytes)
+{
+    scratch_carver c{(char *)base};
+    return {c.take<WD>((size_t)n), c.take<vit_out>((size_t)n), c.take<uint8_t>(path_bytes), c.used};
+}

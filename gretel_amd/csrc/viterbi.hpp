@@ -259,6 +259,24 @@ k_vit_trace(const uint8_t *__restrict__ bp, const double *__restrict__ vend, con
 // host ---------------------------------------------------------------------------------------- (vit_out, vit_bufs: scratch_layout.hpp)
 static const char VIT_SCRATCH[] = "the exact decoder's scratch, whose table grows with N * L and whose back-pointers with N * states,";
 
+// S^L, or one more than the cap where it is beyond it
+static long long vit_states(int S, int L)
+{
+    long long states = 1;
+    for (int k = 0; k < L && states <= GH_VITERBI_MAX_STATES; k++) states *= S;
+    return states;
+}
+
+// the refusal of a window beyond the cap
+static int vit_too_many(const char *who, int S, int L)
+{
+    char cnt[32];
+    const double full = pow((double)S, (double)L);
+    snprintf(cnt, sizeof cnt, full < 1e15 ? "%.0f" : "%.3g", full);
+    return fail(GH_ERR_ARG, "%s: S = %d candidate symbols and Le = min(L, N) = %d make %s states, more than the %d the exact decoder "
+                "holds on chip: lower L, or use the beam (--beam, gh_beam_paths)", who, S, L, cnt, GH_VITERBI_MAX_STATES);
+}
+
 // one exact decoding of the tensor as it stands: the results stay in the handle's scratch (`b`), *ho = hole, score and U
 static int vit_run(gh_handle *h, vit_bufs *b, vit_out *ho, const char *who)
 {
@@ -279,15 +297,8 @@ static int vit_run(gh_handle *h, vit_bufs *b, vit_out *ho, const char *who)
         h->vit_last[0] = 0; h->vit_last[1] = L; h->vit_last[2] = 0; h->vit_last[3] = (int64_t)h->vit.cap;
         return GH_OK;
     }
-    long long states = 1;
-    for (int k = 0; k < L && states <= GH_VITERBI_MAX_STATES; k++) states *= S;
-    if (states > GH_VITERBI_MAX_STATES) {
-        char cnt[32];
-        const double full = pow((double)S, (double)L);
-        snprintf(cnt, sizeof cnt, full < 1e15 ? "%.0f" : "%.3g", full);
-        return fail(GH_ERR_ARG, "%s: S = %d candidate symbols and Le = min(L, N) = %d make %s states, more than the %d the exact decoder "
-                    "holds on chip: lower L, or use the beam (--beam, gh_beam_paths)", who, S, L, cnt, GH_VITERBI_MAX_STATES);
-    }
+    const long long states = vit_states(S, L);
+    if (states > GH_VITERBI_MAX_STATES) return vit_too_many(who, S, L);
     const int ns = (int)states;
     const size_t table_doubles = (size_t)N * beam_src_doubles(L);
     const size_t need = vit_layout(nullptr, N, table_doubles, ns).total;

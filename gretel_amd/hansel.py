@@ -423,6 +423,14 @@ class Hansel:
         bytes of the decoder's device scratch)."""
         return self._info4(self._lib.gh_viterbi_info)
 
+    def viterbi_states(self):
+        """(S, Le, states = S^Le) of the tensor as it stands, without decoding (gh_viterbi_states): what viterbi_path would need.
+        The count is given however large it is (it saturates at 2^63 - 1); the decoder serves up to 4096."""
+        self._ensure()
+        out = np.zeros(3, dtype=np.int64)
+        check(self._lib.gh_viterbi_states(self._h, _p(out)))
+        return tuple(int(v) for v in out)
+
     def clear(self):
         self._staged = []
         if self._h is not None:
@@ -724,6 +732,36 @@ class HanselBatch:
             out.append(dict(n=k, hole_at=int(hole[w]), paths=pw, hp_current=rw[:, 0], hp_original=rw[:, 1], ratio=rw[:, 2],
                             magnitude=rw[:, 3], min_marginal=rw[:, 4]))
         return out
+
+
+    def viterbi_spin(self, max_paths=100, min_remove=0.01):
+        """Hansel.viterbi_spin over every window, the exact decoders of a round side by side in one launch each
+        (gh_panel_viterbi_spin).  One dict per window, shaped as Hansel.viterbi_spin's (ll_chain included), each the result of
+        that call on the window alone.  A window beyond the decoder's cap refuses the whole call before anything is touched
+        (GretelHipError names the window): ask Hansel.viterbi_states() first."""
+        n = len(self.hansels)
+        paths, recs = self._host_buffers(max(1, max_paths))
+        ll = np.zeros((n, max(1, max_paths)))
+        n_out = np.zeros(n, dtype=np.int32)
+        hole = np.zeros(n, dtype=np.int32)
+        check(self._lib.gh_panel_viterbi_spin(self._b, int(max_paths), float(min_remove), _p(paths), _p(self._hb_off), _p(recs), _p(ll),
+                                              _p(n_out), _p(hole)))
+        out = []
+        for w in range(n):
+            k = int(n_out[w])
+            if k:
+                self.hansels[w].is_weighted = True
+            pw, rw = self._hb_win[w][:k].copy(), recs[w, :k].copy()
+            out.append(dict(n=k, hole_at=int(hole[w]), paths=pw, hp_current=rw[:, 0], hp_original=rw[:, 1], ratio=rw[:, 2],
+                            magnitude=rw[:, 3], min_marginal=rw[:, 4], ll_chain=ll[w, :k].copy()))
+        return out
+
+    def viterbi_info(self):
+        """The last viterbi_spin() of this batch (gh_panel_viterbi_info): (windows, rounds run, the most windows one walk launch
+        carried, walk launches in all)."""
+        out = np.zeros(4, dtype=np.int64)
+        check(self._lib.gh_panel_viterbi_info(self._b, _p(out)))
+        return tuple(int(v) for v in out)
 
 
 class HanselPanel(HanselBatch):

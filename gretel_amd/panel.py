@@ -9,6 +9,11 @@ panel (hansel.HanselPanel: the window pipeline over the regions' differing shape
 
 are byte for byte what `python -m gretel_amd.cmd BAM VCF contig -s start -e end -o OUT/<name>` writes with the same options
 (with --assign-reads also OUT/<name>/gretel.support, one assignment call per region).
+--exact recovers every path as the global maximum of the chain likelihood, all regions decoded together as one panel
+(HanselPanel.viterbi_spin: the decoders of a round side by side); a region whose states exceed the decoder's cap gets the
+library's message behind its name, is left out and counts as failed.  --score-paths writes OUT/<name>/gretel.scores, every
+recovered haplotype scored against a copy of the region's matrix taken before the spins (a host loop over the regions).
+--beam and --known are the single CLI's alone: a panel offers neither.
 A region gretel cannot recover (a SNP without pairwise evidence, or no read that carries two SNPs) gets gretel's [FAIL] text on
 stderr behind its name and is left out; the exit status is then 1, once every other region has been written.  Stdout: one line
 per recovered region -- name, SNPs, L, paths, distinct haplotypes.  The single-region debugging options (--debughpos,
@@ -24,6 +29,7 @@ import sys
 from . import __version__
 from . import cmd
 from . import util
+from ._lib import GretelHipError
 from .hansel import HanselPanel
 
 
@@ -40,6 +46,11 @@ def build_parser():
     p.add_argument("--max-depth", type=int, default=8000, help="read-buffer cap of the pileup, as in gretel_amd.cmd [default: 8000]")
     p.add_argument("--pepper", action="store_true", help="permissive read filter (pysam stepper 'all' in the reference)")
     cmd.add_assign_options(p)
+    p.add_argument("--score-paths", action="store_true", help="score every recovered haplotype against the region's unreweighted "
+                   "matrix (chain likelihood, per-SNP margins) and write gretel.scores per region")
+    p.add_argument("--exact", action="store_true", help="recover every path as the global maximum of the chain likelihood (exact "
+                   "decoding over S^min(L, N) states, at most %d), the regions' decoders side by side, instead of the greedy walk"
+                   % cmd.EXACT_MAX_STATES)
     p.add_argument("--version", action="version", version="%(prog)s " + __version__)
     return p
 
@@ -69,7 +80,7 @@ def main(argv=None):
     util.prefetch_bam(args.bam, regions[0]["contig"], regions[0]["start"], regions[0]["end"])
     vcfs = util.process_vcf_regions(args.vcf, regions)
     stepper = "all" if args.pepper else "samtools"
-    kept = []                   # (region, vcf_h, hansel)
+    kept = []                   # (region, vcf_h, hansel, the copy --score-paths scores against or None)
     failed = 0
     for k, (r, vh) in enumerate(zip(regions, vcfs)):
         hansel = None
@@ -93,11 +104,21 @@ def main(argv=None):
             _fail(r["name"], buf.getvalue())
             failed += 1
             continue
-        kept.append((r, vh, hansel))
+        if args.exact:                          # (asked before the spin: one region over the cap would refuse the whole panel)
+            try:
+                states = hansel.viterbi_states()[2]
+                if states > cmd.EXACT_MAX_STATES:
+                    hansel.viterbi_path()       # (raises: the library's own message)
+            except GretelHipError as e:
+                _fail(r["name"], "[FAIL] %s\n" % e)
+                failed += 1
+                continue
+        kept.append((r, vh, hansel, hansel.copy() if args.score_paths else None))       # (as gretel_amd.cmd: before the spins)
     if kept:
-        results = HanselPanel([h for _, _, h in kept]).spin(args.paths, cmd.MIN_REMOVE)
+        panel = HanselPanel([h for _, _, h, _ in kept])
+        results = panel.viterbi_spin(args.paths, cmd.MIN_REMOVE) if args.exact else panel.spin(args.paths, cmd.MIN_REMOVE)
         with open(os.devnull, "w") as quiet:
-            for (r, vh, hansel), res in zip(kept, results):
+            for (r, vh, hansel, unweighted), res in zip(kept, results):
                 paths = cmd.paths_of_spin(hansel, res, log=quiet)
                 dirn = os.path.join(args.out, r["name"])
                 os.makedirs(dirn, exist_ok=True)
@@ -107,6 +128,8 @@ def main(argv=None):
                 if args.assign_reads:
                     ns.min_snps, ns.max_mismatch = args.min_snps, args.max_mismatch
                     cmd.write_support(paths, hansel, ns)
+                if args.score_paths:
+                    cmd.write_scores(paths, unweighted, vh, ns)
                 sys.stdout.write("%s\t%d\t%d\t%d\t%d\n" % (r["name"], vh["N"], hansel.L, res["n"], len(paths)))
     try:                        # (the decoder's kept working buffers: see gretel_amd.cmd)
         from . import bamio

@@ -354,6 +354,43 @@ int gh_viterbi_path(gh_t *h, uint8_t *path_out /*[N+1]*/, double *ll_chain, int 
 int gh_viterbi_spin(gh_t *h, int max_paths, double min_remove, uint8_t *paths_out /*[max_paths][N+1]*/,
                     gh_path_rec *recs, double *ll_chain /*[max_paths], may be NULL*/, int *n_out, int *hole_at);
 int gh_viterbi_info(const gh_t *h, int64_t out[4]);
+/* S, Le and S^Le (saturating at INT64_MAX) of the tensor as it stands, without decoding: out[0..2].  The refusals are those of
+ * gh_viterbi_path short of the cap (a null argument, offer_zero, no fill yet); the count comes back GH_OK however large it is, so
+ * a caller can tell beforehand which windows the decoder serves.  Only the handle's marginal tables are brought up to date. */
+int gh_viterbi_states(gh_t *h, int64_t out[3]);
+
+/* gh_viterbi_spin over every window of a batch or panel, the decoders of a round side by side: a window's exact decoder is ONE
+ * workgroup, so one launch with a workgroup per window decodes all of them in about the time of the slowest.
+ * Window w's paths ([max_paths][N_w + 1] at paths_out + paths_off[w], as gh_panel_spin; for a batch paths_off[w] =
+ * w * max_paths * (N + 1)), recs[w][..], ll_chain[w][..] (may be NULL), n_out[w] and hole_at[w] are what gh_viterbi_spin writes for
+ * that window alone: paths, ll_chain, hp_current, hp_original, min_marginal, ratio and magnitude bit for bit (the reweight is
+ * gh_reweight_path's, window by window).  Afterwards each handle's gh_viterbi_info describes that window's last decoding, and the
+ * tensor, snapshot (taken now where there is none), band, L and fill statistics of each window are as the single spin leaves them.
+ * Round s, for every window still live (fewer than max_paths paths, no hole yet): the chain table of the tensor as it stands (per
+ * window, on its handle's stream); the union, the walk and the trace as one launch each over the live windows (windows that need
+ * the walk without the table ring -- one candidate symbol and Le > 12 -- in a walk launch of their own); the vit_outs and paths
+ * home in two copies; per window the record and the reweight (gh_score_paths, gh_reweight_path).  A window that meets a hole or
+ * its last path drops out; the call ends when no window is live.  No workgroup depends on another: a panel of more windows than
+ * the card holds workgroups finishes all the same.
+ * Stream order: panel launches and copies run on the batch's stream, a window's own work on its handle's; the batch's stream
+ * waits for each handle's by an event, the host waits for the batch's stream before it touches a handle.
+ * Refusals are made as a whole, before any window's tensor, snapshot or scratch is touched: GH_ERR_ARG for a null b, paths_out,
+ * paths_off, recs, n_out or hole_at, for max_paths < 0, a negative offset, a window with offer_zero or a window with more than
+ * GH_VITERBI_MAX_STATES states (gh_viterbi_path's message behind "window <w>: "); GH_ERR_STATE for a window never filled.
+ * max_paths == 0 returns GH_OK with every n_out[w] = 0.  GH_ERR_NOMEM names the window whose scratch cannot be had ((N + 1) *
+ * states back-pointer bytes and the table, as gh_viterbi_path).  Candidate masks only lose bits under a reweight, so round 0's
+ * state count bounds every later round's; the count is checked every round all the same.
+ * gh_panel_viterbi_info, the last such call: out[0] = windows, out[1] = rounds run, out[2] = the most windows one walk launch
+ * carried, out[3] = walk launches in all.
+ * gh_debug_panel_viterbi_phases (measurements only): on != 0 makes every following gh_panel_viterbi_spin of the process wait for
+ * the device after each phase and add up host milliseconds; out (may be NULL) receives what has been added up since the last call
+ * -- [0] table builds (and the call's preamble), [1] union + walk + trace, [2] gather and copies home, [3] records and reweights
+ * -- and the sums start again. */
+int gh_panel_viterbi_spin(gh_batch_t *b, int max_paths, double min_remove, uint8_t *paths_out, const int64_t *paths_off,
+                          gh_path_rec *recs /*[n][max_paths]*/, double *ll_chain /*[n][max_paths], may be NULL*/,
+                          int *n_out /*[n]*/, int *hole_at /*[n]*/);
+int gh_panel_viterbi_info(gh_batch_t *b, int64_t out[4]);
+int gh_debug_panel_viterbi_phases(int on, double out[4]);
 
 /* tensor export/import for --dumpmatrix (gretel/cmd.py:81-82) and tests:
  * band layout [(N+2)][band][7][7] as doubles; dense layout [7][7][N+2][N+2] (gretel/cmd.py:76-77). */
