@@ -162,6 +162,7 @@ def load():
         "gh_viterbi_spin": [vp, i32, dbl, vp, vp, vp, P(i32), P(i32)],
         "gh_viterbi_info": [vp, vp],
         "gh_viterbi_states": [vp, vp],
+        "gh_viterbi_marginals": [vp, vp, vp, P(i32)],
         "gh_panel_viterbi_spin": [vp, i32, dbl, vp, vp, vp, vp, vp, vp],
         "gh_panel_viterbi_info": [vp, vp],
         "gh_debug_panel_viterbi_phases": [i32, vp],

@@ -18,6 +18,12 @@ the chain likelihood; --beam 1 writes what a run without the flag writes.
 and, with --exact (INTEGRATION.md "Exact decoding"), the same files from paths that are each the global maximum of the chain
 likelihood on the matrix at that moment; a window with more than 4096 states ends the run with the library's message, status 1.
 
+and, with --margins (INTEGRATION.md "Max-marginals"), against the matrix as it was before any reweighting:
+    <out>/gretel.margins  "# N L cond_mode marginal_term S states", one "H" line per recovered haplotype (i_0, n_best, max_regret and
+                          the genomic position of argmax_regret) and one "S" line per SNP (genomic position, best allele, gap, the
+                          regret of A C G T - with "." where an allele is not offered); nothing where the window has more than
+                          4096 states (the library's message on stderr, the run goes on)
+
 and, with --score-paths / --known FASTA (INTEGRATION.md "Scoring haplotypes"), against the matrix as it was before any reweighting:
     <out>/gretel.scores   "# N L cond_mode marginal_term" + one line per recovered haplotype: i_0, ll_chain, hp_original, n_greedy,
                           n_on, first_off, min_margin, argmin_margin and the genomic position of argmin_margin
@@ -68,6 +74,9 @@ def build_parser():
     p.add_argument("--exact", action="store_true", help="recover every path as the global maximum of the chain likelihood (exact "
                    "decoding over S^min(L, N) states, at most %d: L <= 6 without deletion columns, L <= 5 with them) instead of "
                    "the greedy walk" % EXACT_MAX_STATES)
+    p.add_argument("--margins", action="store_true", help="compute the max-marginals of the chain likelihood on the unreweighted "
+                   "matrix (per SNP and allele the best likelihood of any haplotype that takes it; the state limit of --exact "
+                   "applies) and write per-SNP confidence gaps and per-haplotype regrets to gretel.margins")
     p.add_argument("--version", action="version", version="%(prog)s " + __version__)
     return p
 
@@ -329,6 +338,51 @@ def write_known(paths, unweighted, vcf_h, args):
         fh.write(scores_text(_score_head(unweighted, vcf_h), names, res, vcf_h["snp_rev"], nearest=near))
 
 
+def _margin_num(v):
+    return "%.6f" % v
+
+
+def margins_text(head, i0s, marg, mm, cm, snp_rev):
+    """gretel.margins: "# N L cond_mode marginal_term S states" (`head`), then one line per haplotype (in the order of `i0s`,
+    out.fasta's) -- "H", i_0, n_best, max_regret, the genomic position of argmax_regret -- then one line per SNP -- "S", the genomic
+    position, the best allele, gap, and the regret of each allele in ACGT- order ("." where it is not offered).  `marg` is
+    margins_of's dict for those haplotypes over Hansel.viterbi_marginals' `mm` and `cm`."""
+    from .hansel import SYMBOLS, margins_of
+    lines = ["# %d\t%d\t%s\t%d\t%d\t%d\n" % tuple(head)]
+    for q, i0 in enumerate(i0s):
+        arg = int(marg["argmax_regret"][q])
+        lines.append("H\t%d\t%d\t%s\t%d\n" % (i0, int(marg["n_best"][q]), _margin_num(marg["max_regret"][q]), snp_rev[arg - 1] if arg > 0 else 0))
+    n = len(cm) - 1
+    alleles = [SYMBOLS.index(c) for c in "ACGT-"]
+    # (the regret of allele s at every SNP is the regret of the constant "path" of s)
+    each = margins_of(mm, cm, [[6] + [s] * n for s in alleles])["regret"]
+    for p in range(1, n + 1):
+        cols = [_margin_num(each[k, p]) if (int(cm[p]) >> s) & 1 else "." for k, s in enumerate(alleles)]
+        lines.append("S\t%d\t%s\t%s\t%s\n" % (snp_rev[p - 1], SYMBOLS[int(marg["best"][p])], _margin_num(marg["gap"][p]), "\t".join(cols)))
+    return "".join(lines)
+
+
+def write_margins(paths, unweighted, vcf_h, args):
+    """--margins: the max-marginals of the copy taken before the spins, read for the distinct haplotypes in out.fasta's order.
+    A window beyond the exact decoder's cap: the library's message on stderr and no file."""
+    from .hansel import margins_of
+    keys = sorted(paths, key=lambda x: paths[x]["i_0"])
+    try:
+        res = unweighted.viterbi_marginals()
+    except GretelHipError as e:
+        sys.stderr.write("[NOTE] --margins: %s\n" % e)
+        return
+    if res["hole_at"]:
+        sys.stderr.write("[NOTE] --margins: no candidate at SNP %d, no max-marginals\n" % res["hole_at"])
+        return
+    order = unweighted._cfg["cand_order"]
+    marg = margins_of(res["mm"], res["cm"], _path_array(paths, keys, unweighted.n), order)
+    s, _, states, _ = unweighted.viterbi_info()
+    with open(args.out + "/gretel.margins", "w") as fh:
+        fh.write(margins_text(_score_head(unweighted, vcf_h) + (s, states), [paths[k]["i_0"] for k in keys], marg, res["mm"], res["cm"],
+                              vcf_h["snp_rev"]))
+
+
 def check_score_options(args):
     """The refusal of --known (before any BAM read or GPU call): a message, or None."""
     if args.known is None:
@@ -408,7 +462,7 @@ def main(argv=None):
                                 stepper="all" if args.pepper else "samtools", keep_reads=args.assign_reads)     # cmd.py:78
     hansel.snapshot_original()                                                    # cmd.py:79 (what the copy is used for)
     # (the reference's copy of cmd.py:79, made only where something is scored against the matrix as the reads filled it)
-    unweighted = hansel.copy() if (args.score_paths or args.known) else None
+    unweighted = hansel.copy() if (args.score_paths or args.known or args.margins) else None
     if args.dumpmatrix:
         hansel.save_hansel_dump(args.dumpmatrix)                                  # cmd.py:81-82
     if gap_report(hansel, vcf_h):
@@ -433,7 +487,9 @@ def main(argv=None):
         write_scores(paths, unweighted, vcf_h, args)
     if args.known:
         write_known(paths, unweighted, vcf_h, args)
-    try:                        # the decoder's kept working buffers (include/gretel_io.h: GIO_KEEP_MB): a run has one decode
+    if args.margins:
+        write_margins(paths, unweighted, vcf_h, args)
+    try:                       # the decoder's kept working buffers (include/gretel_io.h: GIO_KEEP_MB): a run has one decode
         from . import bamio
         if getattr(bamio, "_io", None) is not None:
             bamio.native_release_buffers()

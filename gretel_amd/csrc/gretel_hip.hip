@@ -3447,5 +3447,7 @@ static int check_symbol_rows(const uint8_t *paths, int n_paths, size_t n1, int c
 #include "beam.hpp"
 // exact decoding of the chain likelihood (gh_viterbi_path, gh_viterbi_spin, gh_viterbi_info) -----------
 #include "viterbi.hpp"
+// max-marginals of the chain likelihood: the decoder's forward walk with its scores kept, a backward walk, a parallel reduction
+#include "viterbi_marg.hpp"
 // ... over every window of a batch or panel, the decoders of a round side by side: gh_panel_viterbi_spin, gh_viterbi_states
 #include "viterbi_panel.hpp"

@@ -109,6 +109,29 @@ inline vit_bufs vit_layout(void *base, int N, size_t table_doubles, int states)
     return {out, c.take<double>(table_doubles), c.take<uint8_t>(n1 * ns + 4), c.take<double>(ns), c.take<uint8_t>(ns), c.take<uint8_t>(n1), c.used};
 }
 
+// the max-marginals (viterbi_marg.hpp), in the exact decoder's block of the handle.  `out` is the first part for the same reason as
+// above.  `fb` is the one stored row per position: the forward walk leaves F there, the backward walk puts F + B over it (NaN where
+// a state is not reachable), k_vit_mm reduces it -- N * states doubles, the part that grows (328 MB at 10k SNPs and 4096 states).
+struct vitm_bufs {
+    vit_out *out;
+    double *Gb;
+    double *fb;            // [N][states]: row p - 1 belongs to position p
+    uint8_t *cm5;          // [N + 1] candidate bits over the compact indices, 0 at position 0
+    double *mm;            // [N + 1][7]
+    uint8_t *cm;           // [N + 1] candidate bits over the seven symbols
+    size_t total;
+};
+
+inline vitm_bufs vitm_layout(void *base, int N, size_t table_doubles, int states)
+{
+    scratch_carver c{(char *)base};
+    const size_t n1 = (size_t)N + 1, ns = (size_t)states;
+    vit_out *out = c.take<vit_out>(1);
+    if (!states) return {out, nullptr, nullptr, nullptr, nullptr, nullptr, c.used};
+    return {out, c.take<double>(table_doubles), c.take<double>((size_t)N * ns), c.take<uint8_t>(n1), c.take<double>(n1 * GH_NSYM), c.take<uint8_t>(n1),
+            c.used};
+}
+
 // the exact decoder over a panel (viterbi_panel.hpp), a block of the batch: one descriptor per window (WD = vit_win, which holds
 // device types and so stands in viterbi_panel.hpp), the windows' vit_outs gathered for one copy to the host, and their path rows
 // gathered back to back (`path_bytes` = the sum of N_w + 1)

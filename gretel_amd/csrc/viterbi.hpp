@@ -53,7 +53,11 @@ k_vit_union(const double *__restrict__ minfo, int N, vit_out *__restrict__ out)
 }
 
 // dynamic LDS: [two score rows of `states` doubles] [STAGED: Le + 1 source blocks]
-template <bool STAGED>
+// KEEP (viterbi_marg.hpp): the forward pass of the max-marginals -- the same step, but every score a step writes also goes to
+// global memory by a plain store behind the LDS-only barrier, and no back-pointer, end row or trace is wanted: `vend` is then
+// F[N][states], row p - 1 for position p, and bp and okend are not touched.  The arguments are the same under both, so that the
+// KEEP = false instantiations are the kernels they were.
+template <bool STAGED, bool KEEP = false>
 __global__ void __launch_bounds__(VIT_THREADS)
 k_vit_walk(const double *__restrict__ Gb, int N, int L, int S, int states, int marginal_term, uint32_t U,
            uint8_t *__restrict__ bp, double *__restrict__ vend, uint8_t *__restrict__ okend, vit_out *__restrict__ out)
@@ -169,7 +173,8 @@ k_vit_walk(const double *__restrict__ Gb, int N, int L, int S, int states, int m
                     }
                 }
                 Vn[j] = best;
-                bp[(size_t)p * states + j] = (uint8_t)arg;
+                if (KEEP) vend[(size_t)(p - 1) * states + j] = best;
+                else bp[(size_t)p * states + j] = (uint8_t)arg;
             }
         }
         cur ^= 1;
@@ -177,7 +182,7 @@ k_vit_walk(const double *__restrict__ Gb, int N, int L, int S, int states, int m
         beam_barrier();
     }
     if (tid == 0) out->hole_at = hole;
-    if (!hole) {
+    if (!hole && !KEEP) {
         const double *Vc = V + (size_t)cur * states;
 #pragma unroll
         for (int o = 0; o < VIT_OWN; o++) {
@@ -277,8 +282,17 @@ static int vit_too_many(const char *who, int S, int L)
                 "holds on chip: lower L, or use the beam (--beam, gh_beam_paths)", who, S, L, cnt, GH_VITERBI_MAX_STATES);
 }
 
-// one exact decoding of the tensor as it stands: the results stay in the handle's scratch (`b`), *ho = hole, score and U
-static int vit_run(gh_handle *h, vit_bufs *b, vit_out *ho, const char *who)
+// GH_VIT_STAGE=0, read once (A/B: the table blocks from global memory)
+static bool vit_no_stage()
+{
+    static const bool off = env_off("GH_VIT_STAGE");
+    return off;
+}
+
+// What the decoder and the max-marginals (viterbi_marg.hpp) open a call with: U of the tensor as it stands (ho->U, S its bits)
+// and *ns = S^Le, refused beyond the cap.  *ns = 0 where nothing is offered anywhere: ho->hole_at = 1 and the call is over.  The
+// vit_out is the first part of the handle's block under either layout (scratch_layout.hpp).
+static int vit_open(gh_handle *h, vit_out *ho, const char *who, int *ns)
 {
     const int N = h->N, L = chain_lags(h);
     int rc = ensure_marg(h);                                    // (k_vit_union reads minfo)
@@ -290,8 +304,8 @@ static int vit_run(gh_handle *h, vit_bufs *b, vit_out *ho, const char *who)
     if ((rc = post_launch(h, "k_vit_union"))) return rc;
     HIPCHK(hipMemcpyAsync(ho, d_out, sizeof *ho, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    const uint32_t U = ho->U;
-    const int S = __builtin_popcount(U);
+    const int S = __builtin_popcount(ho->U);
+    *ns = 0;
     if (S == 0) {                                             // nothing offered anywhere: the hole is the first position
         ho->hole_at = 1;
         h->vit_last[0] = 0; h->vit_last[1] = L; h->vit_last[2] = 0; h->vit_last[3] = (int64_t)h->vit.cap;
@@ -299,14 +313,25 @@ static int vit_run(gh_handle *h, vit_bufs *b, vit_out *ho, const char *who)
     }
     const long long states = vit_states(S, L);
     if (states > GH_VITERBI_MAX_STATES) return vit_too_many(who, S, L);
-    const int ns = (int)states;
+    *ns = (int)states;
+    return GH_OK;
+}
+
+// one exact decoding of the tensor as it stands: the results stay in the handle's scratch (`b`), *ho = hole, score and U
+static int vit_run(gh_handle *h, vit_bufs *b, vit_out *ho, const char *who)
+{
+    const int N = h->N, L = chain_lags(h);
+    int rc, ns;
+    if ((rc = vit_open(h, ho, who, &ns)) || !ns) return rc;
+    const uint32_t U = ho->U;
+    const int S = __builtin_popcount(U);
     const size_t table_doubles = (size_t)N * beam_src_doubles(L);
     const size_t need = vit_layout(nullptr, N, table_doubles, ns).total;
     if ((rc = scratch_reserve(h, &h->vit, need, VIT_SCRATCH))) return rc;
     *b = vit_layout(h->vit.buf, N, table_doubles, ns);
     if ((rc = chain_table_build(h, L, b->Gb))) return rc;
 
-    static const bool no_stage = env_off("GH_VIT_STAGE");       // (A/B: the table blocks from global memory)
+    const bool no_stage = vit_no_stage();
     const size_t rows = 2 * (size_t)ns * 8;
     if (!no_stage && L <= VIT_MAX_LE) {                         // (a longer state has S = 1: its ring need not fit)
         const size_t lds = rows + (size_t)(L + 1) * beam_src_doubles(L) * 8;

@@ -64,6 +64,63 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def margins_of(mm, cm, paths, cand_order="ACGT-"):
+    """What Hansel.viterbi_marginals()' table says per SNP and about the haplotypes `paths` (uint8[H][N+1], or one uint8[N+1]).
+    Host only, no handle.  mm float64[N+1][7], cm uint8[N+1].  Returns a dict:
+      best uint8[N+1]      the candidate of largest max-marginal, the first of cand_order among the maximisers (6, '_', at 0);
+      gap float64[N+1]     mm[p][best] minus the largest OTHER offered entry: the exact phasing confidence of the call at p.  +inf
+                           where nothing else is offered or the largest other is -inf; 0.0 where every entry is -inf (and at 0);
+      regret float64[H][N+1]  mm[p][best[p]] - mm[p][x[p]]: what the best full path through x[p] lacks to the best of all.  +inf
+                           where x[p] is not offered, or its entry is -inf while the best is finite; 0.0 where both are -inf;
+      max_regret float64[H], argmax_regret int32[H] (the first position that has it), n_best int32[H] (positions where
+      x[p] == best[p])."""
+    mm = np.asarray(mm, dtype=np.float64)
+    cm = np.asarray(cm, dtype=np.uint8)
+    n = len(cm) - 1
+    x = np.asarray(paths, dtype=np.uint8)
+    if x.ndim == 1:
+        x = x.reshape(1, -1) if x.size else x.reshape(0, n + 1)
+    if mm.shape != (n + 1, 7) or x.ndim != 2 or x.shape[1] != n + 1:
+        raise ValueError("margins_of: mm must be [N+1][7], cm [N+1] and paths [H][N+1] (got %s, %s, %s)" % (mm.shape, cm.shape, x.shape))
+    order = [SYMBOLS.index(c) for c in cand_order]
+    best = np.full(n + 1, 6, dtype=np.uint8)
+    gap = np.zeros(n + 1)
+    ninf = float("-inf")
+    for p in range(1, n + 1):
+        offered = [s for s in order if (int(cm[p]) >> s) & 1]
+        if not offered:
+            continue
+        b = offered[0]
+        for s in offered[1:]:
+            if mm[p, s] > mm[p, b]:
+                b = s
+        best[p] = b
+        other = max((float(mm[p, s]) for s in offered if s != b), default=ninf)
+        if mm[p, b] == ninf:
+            gap[p] = 0.0
+        elif other == ninf:
+            gap[p] = np.inf
+        else:
+            gap[p] = mm[p, b] - other
+    regret = np.zeros(x.shape)
+    for q, row in enumerate(x):
+        for p in range(1, n + 1):
+            s, top = int(row[p]), float(mm[p, best[p]])
+            if s > 6 or not (int(cm[p]) >> s) & 1:
+                regret[q, p] = np.inf
+            elif mm[p, s] == ninf:
+                regret[q, p] = 0.0 if top == ninf else np.inf
+            else:
+                regret[q, p] = top - mm[p, s]
+    if n:
+        arg = (regret[:, 1:].argmax(axis=1) + 1).astype(np.int32)
+        mx = regret[np.arange(len(x)), arg]
+    else:
+        arg, mx = np.zeros(len(x), dtype=np.int32), np.zeros(len(x))
+    return dict(best=best, gap=gap, regret=regret, max_regret=mx, argmax_regret=arg,
+                n_best=(x[:, 1:] == best[None, 1:]).sum(axis=1).astype(np.int32))
+
+
 class Hansel:
     def __init__(self, n_snps, band=None, storage="f32", cond_mode="A", marginal_term=False, device=-1,
                  cand_order="ACGT-", offer_zero=False):
@@ -422,6 +479,21 @@ class Hansel:
         """The last exact decoding on this handle (gh_viterbi_info): (S candidate symbols, Le = min(L, N), states = S^Le,
         bytes of the decoder's device scratch)."""
         return self._info4(self._lib.gh_viterbi_info)
+
+    def viterbi_marginals(self):
+        """The max-marginals of the chain likelihood on the tensor as it is now (gh_viterbi_marginals; the definition:
+        INTEGRATION.md "Max-marginals"): per SNP p and symbol s the best chain likelihood of any full path that takes s at p.
+        Returns dict(mm float64[N+1][7], cm uint8[N+1] the candidate bits over the seven symbols, hole_at); entries of symbols
+        not offered are -inf; at a hole mm and cm are None.  Served where viterbi_path() is; margins_of() reads the table.  The
+        tensor is not touched."""
+        self._ensure()
+        mm = np.full((self.n + 1, 7), -np.inf)
+        cm = np.zeros(self.n + 1, dtype=np.uint8)
+        hole = C.c_int()
+        check(self._lib.gh_viterbi_marginals(self._h, _p(mm), _p(cm), C.byref(hole)))
+        if hole.value:
+            return dict(mm=None, cm=None, hole_at=hole.value)
+        return dict(mm=mm, cm=cm, hole_at=0)
 
     def viterbi_states(self):
         """(S, Le, states = S^Le) of the tensor as it stands, without decoding (gh_viterbi_states): what viterbi_path would need.

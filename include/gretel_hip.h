@@ -359,6 +359,37 @@ int gh_viterbi_info(const gh_t *h, int64_t out[4]);
  * a caller can tell beforehand which windows the decoder serves.  Only the handle's marginal tables are brought up to date. */
 int gh_viterbi_states(gh_t *h, int64_t out[3]);
 
+/* Max-marginals of the chain likelihood (no reference counterpart; INTEGRATION.md "Max-marginals").  gh_score_paths' margin says
+ * what one greedy step would have lost with the history held fixed; this says, for every SNP p and every candidate c, the best
+ * chain likelihood of ANY full path that takes c at p -- everything else free to re-optimise around the choice.  Notation as in
+ * "Exact decoding" above.  A state at p is the last min(Le, p) picks; it is reachable where each of its picks is offered at its
+ * position.
+ *   Forward.  F_0(()) = +0.0.  F_p(s) = the maximum over the reachable predecessors s' of  F_{p-1}(s') + w_p(newest(s) | s'):  one
+ *   binary64 addition, plain >.  (The scores the exact decoder keeps per state.)
+ *   Backward.  B_N(s) = +0.0 for every reachable s.  For p < N, B_p(s) = the maximum over c in cm(p+1) of
+ *   w_{p+1}(c | s) + B_{p+1}(s.c):  one addition, the weight on the left, w summed in the definition's order (the marginal term,
+ *   then lags 1, 2, ..., Le) before it meets B.
+ *   Max-marginal.  For p = 1..N and c in cm(p):  M[p][c] = the maximum of  F_p(s) + B_p(s)  -- one addition -- over the reachable
+ *   states s at p whose newest pick is c.  A maximum of doubles does not depend on the order and there are no NaNs (offer_zero is
+ *   refused), so there is no tie rule.  -inf is a value like any other.
+ *   Exactness.  fl(+) is monotone in each argument, so M[p][c] equals, bit for bit, the maximum over all full paths x with
+ *   x[p] = c of fl(fwd_p(x) + bwd_p(x)):  fwd_p the sequential sum of w_1 .. w_p in ascending order from +0.0;  bwd_p from +0.0,
+ *   b <- w_t + b for t = N down to p + 1.
+ *   Output.  mm[N+1][7] by symbol index: entries of symbols not offered at p are -inf, row 0 is all -inf.  cm[N+1]: the candidate
+ *   bits over the seven symbols (bit s = symbol s offered), which tell an offered -inf from "not offered"; cm[0] = 0.  Hole: at
+ *   the first p with empty cm(p), hole_at = p and neither mm nor cm is written.  Otherwise hole_at = 0.
+ *   Hence  max_c mm[N][c] == gh_viterbi_path's ll_chain  exactly (B_N = +0.0), and every finite entry lies within N * 2^-52 * A of
+ *   the sequentially summed maximum gh_score_paths would give over the paths through (p, c), A the largest sum of |w_t| over
+ *   full paths (two summation orders of N terms); an entry is -inf exactly where that maximum is.
+ * The refusals are gh_viterbi_path's: GH_ERR_ARG for a null argument, offer_zero, or more than GH_VITERBI_MAX_STATES states (the
+ * same message); GH_ERR_STATE before any fill.  GH_ERR_NOMEM names the size of the scratch, which is the exact decoder's block of
+ * the handle (kept until gh_destroy) and here holds the table, ONE stored row of S^Le doubles per position -- N * S^Le * 8 bytes,
+ * 82 MB at 10k SNPs and 1024 states, 328 MB at 4096; it is not bounded by checkpointing -- and mm and cm.  The forward walk stores
+ * F there, the backward walk puts F + B over it, a parallel kernel takes the maxima.
+ * It only reads the tensor: the band, L, the fill statistics, the snapshot, the handle's conditional tables and the results of a
+ * following gh_spin stay as they are, bit for bit.  gh_viterbi_info afterwards describes this call: S, Le, states, scratch bytes. */
+int gh_viterbi_marginals(gh_t *h, double *mm /*[N+1][7]*/, uint8_t *cm /*[N+1]*/, int *hole_at);
+
 /* gh_viterbi_spin over every window of a batch or panel, the decoders of a round side by side: a window's exact decoder is ONE
  * workgroup, so one launch with a workgroup per window decodes all of them in about the time of the slowest.
  * Window w's paths ([max_paths][N_w + 1] at paths_out + paths_off[w], as gh_panel_spin; for a batch paths_off[w] =
