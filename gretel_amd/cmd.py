@@ -43,6 +43,9 @@ from .hansel import Hansel
 MIN_REMOVE = 0.01          # cmd.py:157
 BEAM_MAX = 32              # include/gretel_hip.h: GH_BEAM_MAX
 EXACT_MAX_STATES = 4096    # include/gretel_hip.h: GH_VITERBI_MAX_STATES
+MARGINS_HELP = ("compute the max-marginals of the chain likelihood on the unreweighted matrix (per SNP and allele the best likelihood "
+                "of any haplotype that takes it; the state limit of --exact applies) and write per-SNP confidence gaps and "
+                "per-haplotype regrets to gretel.margins")          # (gretel_amd.panel's --margins says the same)
 
 
 def build_parser():
@@ -74,9 +77,7 @@ def build_parser():
     p.add_argument("--exact", action="store_true", help="recover every path as the global maximum of the chain likelihood (exact "
                    "decoding over S^min(L, N) states, at most %d: L <= 6 without deletion columns, L <= 5 with them) instead of "
                    "the greedy walk" % EXACT_MAX_STATES)
-    p.add_argument("--margins", action="store_true", help="compute the max-marginals of the chain likelihood on the unreweighted "
-                   "matrix (per SNP and allele the best likelihood of any haplotype that takes it; the state limit of --exact "
-                   "applies) and write per-SNP confidence gaps and per-haplotype regrets to gretel.margins")
+    p.add_argument("--margins", action="store_true", help=MARGINS_HELP)
     p.add_argument("--version", action="version", version="%(prog)s " + __version__)
     return p
 
@@ -362,25 +363,31 @@ def margins_text(head, i0s, marg, mm, cm, snp_rev):
     return "".join(lines)
 
 
+def write_margins_result(paths, res, head, order, vcf_h, args, name=None):
+    """What follows the max-marginals call, for this CLI and for gretel_amd.panel (which makes one call for all its regions): `res`
+    is Hansel.viterbi_marginals' dict, `head` the header's six figures (N, L, cond_mode, marginal_term, S, states -- S and states
+    as the call left them), `order` the handle's cand_order.  At a hole the note on stderr (behind `name` where there is one)
+    and no file; otherwise gretel.margins for the distinct haplotypes in out.fasta's order."""
+    from .hansel import margins_of
+    if res["hole_at"]:
+        sys.stderr.write("%s[NOTE] --margins: no candidate at SNP %d, no max-marginals\n" % ("%s: " % name if name else "", res["hole_at"]))
+        return
+    keys = sorted(paths, key=lambda x: paths[x]["i_0"])
+    marg = margins_of(res["mm"], res["cm"], _path_array(paths, keys, len(res["cm"]) - 1), order)
+    with open(args.out + "/gretel.margins", "w") as fh:
+        fh.write(margins_text(head, [paths[k]["i_0"] for k in keys], marg, res["mm"], res["cm"], vcf_h["snp_rev"]))
+
+
 def write_margins(paths, unweighted, vcf_h, args):
     """--margins: the max-marginals of the copy taken before the spins, read for the distinct haplotypes in out.fasta's order.
     A window beyond the exact decoder's cap: the library's message on stderr and no file."""
-    from .hansel import margins_of
-    keys = sorted(paths, key=lambda x: paths[x]["i_0"])
     try:
         res = unweighted.viterbi_marginals()
     except GretelHipError as e:
         sys.stderr.write("[NOTE] --margins: %s\n" % e)
         return
-    if res["hole_at"]:
-        sys.stderr.write("[NOTE] --margins: no candidate at SNP %d, no max-marginals\n" % res["hole_at"])
-        return
-    order = unweighted._cfg["cand_order"]
-    marg = margins_of(res["mm"], res["cm"], _path_array(paths, keys, unweighted.n), order)
     s, _, states, _ = unweighted.viterbi_info()
-    with open(args.out + "/gretel.margins", "w") as fh:
-        fh.write(margins_text(_score_head(unweighted, vcf_h) + (s, states), [paths[k]["i_0"] for k in keys], marg, res["mm"], res["cm"],
-                              vcf_h["snp_rev"]))
+    write_margins_result(paths, res, _score_head(unweighted, vcf_h) + (s, states), unweighted._cfg["cand_order"], vcf_h, args)
 
 
 def check_score_options(args):

@@ -2416,6 +2416,7 @@ struct gh_batch {
     dev_scratch vit;
     std::vector<hipEvent_t> vit_ev;
     int64_t vit_info[4];
+    int64_t vitm_info[4];       // gh_panel_viterbi_marginals_info (viterbi_marg_panel.hpp: the same block and events)
 };
 
 extern "C" int gh_batch_destroy(gh_batch_t *b)
@@ -3451,3 +3452,5 @@ static int check_symbol_rows(const uint8_t *paths, int n_paths, size_t n1, int c
 #include "viterbi_marg.hpp"
 // ... over every window of a batch or panel, the decoders of a round side by side: gh_panel_viterbi_spin, gh_viterbi_states
 #include "viterbi_panel.hpp"
+// ... and the max-marginals over every window: gh_panel_viterbi_marginals
+#include "viterbi_marg_panel.hpp"

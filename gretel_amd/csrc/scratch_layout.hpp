@@ -147,3 +147,23 @@ template <typename WD> inline vit_panel_bufs<WD> vit_panel_layout(void *base, in
     scratch_carver c{(char *)base};
     return {c.take<WD>((size_t)n), c.take<vit_out>((size_t)n), c.take<uint8_t>(path_bytes), c.used};
 }
+
+// the max-marginals over a panel (viterbi_marg_panel.hpp), in the same block of the batch: one descriptor per window in window
+// order (WD = vitm_win), the launch lists (window indices: the forward walk's launches in the first n ints, the backward walk's
+// in the second n), the windows' vit_outs gathered for one copy to the host, and their mm and cm gathered back to back in window
+// order (`positions` = the sum of N_w + 1: window w's mm at 7 * home_w doubles, its cm at home_w bytes, home_w the sum before it)
+template <typename WD> struct vitm_panel_bufs {
+    WD *wd;
+    int32_t *list;         // [2 n]
+    vit_out *outs;         // [n]
+    double *mm;            // [positions][7]
+    uint8_t *cm;           // [positions]
+    size_t total;
+};
+
+template <typename WD> inline vitm_panel_bufs<WD> vitm_panel_layout(void *base, int n, size_t positions)
+{
+    scratch_carver c{(char *)base};
+    return {c.take<WD>((size_t)n), c.take<int32_t>(2 * (size_t)n), c.take<vit_out>((size_t)n), c.take<double>(positions * GH_NSYM),
+            c.take<uint8_t>(positions), c.used};
+}

@@ -52,7 +52,8 @@ __device__ __forceinline__ void vit_union_body(const double *__restrict__ minfo,
 
 
 // dynamic LDS: [two score rows of `states` doubles] [STAGED: Le + 1 source blocks]
-template <bool STAGED>
+// KEEP (viterbi_marg_panel.hpp): as k_vit_walk's -- `vend` is F[N][states], no back-pointers, no end row
+template <bool STAGED, bool KEEP = false>
 __device__ __forceinline__ void
 vit_walk_body(const double *__restrict__ Gb, int N, int L, int S, int states, int marginal_term, uint32_t U,
               uint8_t *__restrict__ bp, double *__restrict__ vend, uint8_t *__restrict__ okend, vit_out *__restrict__ out)
@@ -168,7 +169,8 @@ vit_walk_body(const double *__restrict__ Gb, int N, int L, int S, int states, in
                     }
                 }
                 Vn[j] = best;
-                bp[(size_t)p * states + j] = (uint8_t)arg;
+                if (KEEP) vend[(size_t)(p - 1) * states + j] = best;
+                else bp[(size_t)p * states + j] = (uint8_t)arg;
             }
         }
         cur ^= 1;
@@ -176,7 +178,7 @@ vit_walk_body(const double *__restrict__ Gb, int N, int L, int S, int states, in
         beam_barrier();
     }
     if (tid == 0) out->hole_at = hole;
-    if (!hole) {
+    if (!hole && !KEEP) {
         const double *Vc = V + (size_t)cur * states;
 #pragma unroll
         for (int o = 0; o < VIT_OWN; o++) {

@@ -836,6 +836,38 @@ class HanselBatch:
         return tuple(int(v) for v in out)
 
 
+    def viterbi_marginals(self):
+        """Hansel.viterbi_marginals over every window, the forward walks side by side in one launch and the backward walks in
+        another (gh_panel_viterbi_marginals).  One dict per window, shaped as Hansel.viterbi_marginals': mm float64[n+1][7], cm
+        uint8[n+1], hole_at; mm and cm are None at a hole.  Each window gets its own arrays, each the result of that call on
+        the window alone.  The tensors are not touched.  A window beyond the decoder's cap refuses the whole call before
+        anything is touched (GretelHipError names the window): ask Hansel.viterbi_states() first.  The scratch is the sum of
+        the windows' N * states * 8 bytes."""
+        n = len(self.hansels)
+        n1s = np.asarray([h.n + 1 for h in self.hansels], dtype=np.int64)
+        off = np.zeros(n, dtype=np.int64)
+        off[1:] = np.cumsum(n1s[:-1])
+        mm = np.full((int(n1s.sum()), 7), -np.inf)
+        cm = np.zeros(int(n1s.sum()), dtype=np.uint8)
+        hole = np.zeros(n, dtype=np.int32)
+        check(self._lib.gh_panel_viterbi_marginals(self._b, _p(mm), _p(cm), _p(off), _p(hole)))
+        out = []
+        for w in range(n):
+            if hole[w]:
+                out.append(dict(mm=None, cm=None, hole_at=int(hole[w])))
+            else:
+                a, e = int(off[w]), int(off[w] + n1s[w])
+                out.append(dict(mm=mm[a:e].copy(), cm=cm[a:e].copy(), hole_at=0))
+        return out
+
+    def viterbi_marginals_info(self):
+        """The last viterbi_marginals() of this batch (gh_panel_viterbi_marginals_info): (windows, windows that met a hole, walk
+        launches -- forward and backward together --, scratch bytes summed over the handles' blocks)."""
+        out = np.zeros(4, dtype=np.int64)
+        check(self._lib.gh_panel_viterbi_marginals_info(self._b, _p(out)))
+        return tuple(int(v) for v in out)
+
+
 class HanselPanel(HanselBatch):
     """Many windows of DIFFERING shape recovered together (gh_panel_*): one region (gene) per window, each with its own n_snps,
     band and L.  The windows go in one group per L; the window pipeline (csrc/wpipe.hpp) carries every group it can, gh_spin

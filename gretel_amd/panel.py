@@ -13,6 +13,9 @@ are byte for byte what `python -m gretel_amd.cmd BAM VCF contig -s start -e end 
 (HanselPanel.viterbi_spin: the decoders of a round side by side); a region whose states exceed the decoder's cap gets the
 library's message behind its name, is left out and counts as failed.  --score-paths writes OUT/<name>/gretel.scores, every
 recovered haplotype scored against a copy of the region's matrix taken before the spins (a host loop over the regions).
+--margins writes OUT/<name>/gretel.margins, the max-marginals of the region's matrix before the spins, all regions' walks side
+by side (HanselPanel.viterbi_marginals); without --exact a region beyond the decoder's cap gets the library's message as a
+[NOTE] behind its name and no such file, its other files are written and the exit status is unaffected.
 --beam and --known are the single CLI's alone: a panel offers neither.
 A region gretel cannot recover (a SNP without pairwise evidence, or no read that carries two SNPs) gets gretel's [FAIL] text on
 stderr behind its name and is left out; the exit status is then 1, once every other region has been written.  Stdout: one line
@@ -51,6 +54,7 @@ def build_parser():
     p.add_argument("--exact", action="store_true", help="recover every path as the global maximum of the chain likelihood (exact "
                    "decoding over S^min(L, N) states, at most %d), the regions' decoders side by side, instead of the greedy walk"
                    % cmd.EXACT_MAX_STATES)
+    p.add_argument("--margins", action="store_true", help=cmd.MARGINS_HELP)
     p.add_argument("--version", action="version", version="%(prog)s " + __version__)
     return p
 
@@ -81,6 +85,7 @@ def main(argv=None):
     vcfs = util.process_vcf_regions(args.vcf, regions)
     stepper = "all" if args.pepper else "samtools"
     kept = []                   # (region, vcf_h, hansel, the copy --score-paths scores against or None)
+    served = []                 # --margins: indices into kept of the regions the max-marginals serve
     failed = 0
     for k, (r, vh) in enumerate(zip(regions, vcfs)):
         hansel = None
@@ -104,6 +109,7 @@ def main(argv=None):
             _fail(r["name"], buf.getvalue())
             failed += 1
             continue
+        margins_ok = True
         if args.exact:                          # (asked before the spin: one region over the cap would refuse the whole panel)
             try:
                 states = hansel.viterbi_states()[2]
@@ -113,12 +119,28 @@ def main(argv=None):
                 _fail(r["name"], "[FAIL] %s\n" % e)
                 failed += 1
                 continue
+        elif args.margins:                      # (asked beforehand likewise; here a region over the cap only goes without the file)
+            try:
+                if hansel.viterbi_states()[2] > cmd.EXACT_MAX_STATES:
+                    hansel.viterbi_marginals()  # (raises: the library's own message)
+            except GretelHipError as e:
+                _fail(r["name"], "[NOTE] --margins: %s\n" % e)
+                margins_ok = False
+        if args.margins and margins_ok:
+            served.append(len(kept))
         kept.append((r, vh, hansel, hansel.copy() if args.score_paths else None))       # (as gretel_amd.cmd: before the spins)
+    margins = {}                # index into kept -> (viterbi_marginals' dict, the header's figures), taken before the spins
+    if served:
+        # (the call only reads the tensors: the live handles, no copy; S and states now -- an exact spin overwrites viterbi_info)
+        hs = [kept[k][2] for k in served]
+        for k, h, res in zip(served, hs, HanselPanel(hs).viterbi_marginals()):
+            s, _, states, _ = h.viterbi_info()
+            margins[k] = (res, cmd._score_head(h, kept[k][1]) + (s, states))
     if kept:
         panel = HanselPanel([h for _, _, h, _ in kept])
         results = panel.viterbi_spin(args.paths, cmd.MIN_REMOVE) if args.exact else panel.spin(args.paths, cmd.MIN_REMOVE)
         with open(os.devnull, "w") as quiet:
-            for (r, vh, hansel, unweighted), res in zip(kept, results):
+            for k, ((r, vh, hansel, unweighted), res) in enumerate(zip(kept, results)):
                 paths = cmd.paths_of_spin(hansel, res, log=quiet)
                 dirn = os.path.join(args.out, r["name"])
                 os.makedirs(dirn, exist_ok=True)
@@ -130,6 +152,8 @@ def main(argv=None):
                     cmd.write_support(paths, hansel, ns)
                 if args.score_paths:
                     cmd.write_scores(paths, unweighted, vh, ns)
+                if k in margins:
+                    cmd.write_margins_result(paths, margins[k][0], margins[k][1], hansel._cfg["cand_order"], vh, ns, name=r["name"])
                 sys.stdout.write("%s\t%d\t%d\t%d\t%d\n" % (r["name"], vh["N"], hansel.L, res["n"], len(paths)))
     try:                        # (the decoder's kept working buffers: see gretel_amd.cmd)
         from . import bamio

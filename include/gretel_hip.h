@@ -423,6 +423,39 @@ int gh_panel_viterbi_spin(gh_batch_t *b, int max_paths, double min_remove, uint8
 int gh_panel_viterbi_info(gh_batch_t *b, int64_t out[4]);
 int gh_debug_panel_viterbi_phases(int on, double out[4]);
 
+/* gh_viterbi_marginals over every window of a batch or panel, the walks side by side: a window's forward walk and its backward
+ * walk are ONE workgroup each, so one launch with a workgroup per window does every window's in about the time of the slowest.
+ * Window w's mm ([N_w + 1][7] doubles at mm + 7 * pos_off[w]), cm ([N_w + 1] bytes at cm + pos_off[w]) and hole_at[w] are what
+ * gh_viterbi_marginals writes for that handle alone, as IEEE values, -inf included.  pos_off is in positions; the running sum of
+ * N_v + 1 packs the windows back to back.  A window that meets a hole has neither of its ranges written; the others run on.
+ * Afterwards each handle's gh_viterbi_info is what the single call would have left (S, Le, states, the bytes of that window's
+ * block).  The call only reads the tensors: for every window the band, L, the fill statistics, the snapshot, the conditional
+ * tables and the results of a following gh_spin / gh_panel_spin stay as they are, bit for bit.
+ * Launches: the candidate bits of all windows in one (2-D: y the window); the forward walks in one, and a second for the windows
+ * that walk without the table ring (one candidate symbol and Le > 12, or GH_VIT_STAGE=0); the backward walks in one for the
+ * windows whose four rows and ring fit 160 KB of LDS and a second for the others (two symbols and Le >= 11, for one) -- the
+ * single call's decision, window by window; the maxima in one; a gather of the vit_outs, mm and cm, then one copy home each
+ * where the caller's offsets are the running sum and no window met a hole (one more pair per break otherwise).  No workgroup
+ * depends on another: a panel of more windows than the card holds workgroups finishes all the same.
+ * Scratch: each window's block is its handle's own exact-decoder block under the max-marginals' layout, exactly as the single
+ * call reserves it (kept until gh_destroy); all blocks are reserved before the first walk is launched.  There is no wave or budget
+ * scheme: the panel asks for the sum over its windows of N * states * 8 bytes plus the tables and the small parts -- 64 windows of
+ * 10 000 SNPs at 1 024 states are 6 GB.  GH_ERR_NOMEM names the window that could not be served and that sum.  The descriptors,
+ * the launch lists and the gathered results ((N_w + 1) * 57 bytes a window) are a block of the batch, shared with
+ * gh_panel_viterbi_spin.
+ * Stream order: a window's marginal tables and chain table on its handle's stream, an event per window before the batch's
+ * stream, everything panel-wide on the batch's stream; the host waits for the batch's stream before it touches a handle.
+ * Refusals are made as a whole, before any window's scratch or gh_viterbi_info is touched: GH_ERR_ARG for a null b, mm, cm,
+ * pos_off or hole_at, a negative offset, a window with offer_zero or a window with more than GH_VITERBI_MAX_STATES states
+ * (gh_viterbi_path's message behind "window <w>: "); GH_ERR_STATE for a window never filled.
+ * gh_panel_viterbi_marginals_info, the last such call: out[0] = windows, out[1] = windows that met a hole, out[2] = walk
+ * launches, forward and backward together, out[3] = scratch bytes summed over the handles' blocks.  GH_ERR_ARG for a null
+ * argument.
+ * Under gh_debug_panel_viterbi_phases (measurements only) this call adds up too: [0] the preamble, the table builds and the
+ * candidate bits, [1] the forward walks, [2] the backward walks, [3] the maxima, the gather and the copies home. */
+int gh_panel_viterbi_marginals(gh_batch_t *b, double *mm, uint8_t *cm, const int64_t *pos_off /*[n]*/, int *hole_at /*[n]*/);
+int gh_panel_viterbi_marginals_info(gh_batch_t *b, int64_t out[4]);
+
 /* tensor export/import for --dumpmatrix (gretel/cmd.py:81-82) and tests:
  * band layout [(N+2)][band][7][7] as doubles; dense layout [7][7][N+2][N+2] (gretel/cmd.py:76-77). */
 int gh_export_band(gh_t *h, double *out);
