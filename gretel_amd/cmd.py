@@ -24,6 +24,12 @@ and, with --margins (INTEGRATION.md "Max-marginals"), against the matrix as it w
                           regret of A C G T - with "." where an allele is not offered); nothing where the window has more than
                           4096 states (the library's message on stderr, the run goes on)
 
+and, with --kbest K (INTEGRATION.md "K-best decoding"), against the matrix as it was before any reweighting:
+    <out>/gretel.kbest    "# N L cond_mode marginal_term S states K n" + one line per rank of the K exactly best haplotypes of the
+                          chain likelihood: rank, ll_chain, gap to rank 0, hamming0 (SNPs that differ from rank 0), the i_0 of the
+                          nearest recovered haplotype, the number of SNPs at which they differ, and the SNP string; nothing where
+                          K lists of the window's states do not fit 4096 slots or at a hole (a note on stderr, the run goes on)
+
 and, with --score-paths / --known FASTA (INTEGRATION.md "Scoring haplotypes"), against the matrix as it was before any reweighting:
     <out>/gretel.scores   "# N L cond_mode marginal_term" + one line per recovered haplotype: i_0, ll_chain, hp_original, n_greedy,
                           n_on, first_off, min_margin, argmin_margin and the genomic position of argmin_margin
@@ -43,6 +49,7 @@ from .hansel import Hansel
 MIN_REMOVE = 0.01          # cmd.py:157
 BEAM_MAX = 32              # include/gretel_hip.h: GH_BEAM_MAX
 EXACT_MAX_STATES = 4096    # include/gretel_hip.h: GH_VITERBI_MAX_STATES
+KBEST_MAX = 32             # include/gretel_hip.h: GH_KBEST_MAX
 MARGINS_HELP = ("compute the max-marginals of the chain likelihood on the unreweighted matrix (per SNP and allele the best likelihood "
                 "of any haplotype that takes it; the state limit of --exact applies) and write per-SNP confidence gaps and "
                 "per-haplotype regrets to gretel.margins")          # (gretel_amd.panel's --margins says the same)
@@ -78,6 +85,9 @@ def build_parser():
                    "decoding over S^min(L, N) states, at most %d: L <= 6 without deletion columns, L <= 5 with them) instead of "
                    "the greedy walk" % EXACT_MAX_STATES)
     p.add_argument("--margins", action="store_true", help=MARGINS_HELP)
+    p.add_argument("--kbest", type=int, default=None, metavar="K", help="find the K exactly best haplotypes of the chain likelihood on "
+                   "the unreweighted matrix (1..%d; K times the states of --exact must not exceed %d) and write them, their gaps "
+                   "and the nearest recovered haplotype to gretel.kbest" % (KBEST_MAX, EXACT_MAX_STATES))
     p.add_argument("--version", action="version", version="%(prog)s " + __version__)
     return p
 
@@ -390,6 +400,47 @@ def write_margins(paths, unweighted, vcf_h, args):
     write_margins_result(paths, res, _score_head(unweighted, vcf_h) + (s, states), unweighted._cfg["cand_order"], vcf_h, args)
 
 
+def kbest_text(head, res, per_rank, i0s):
+    """gretel.kbest: "# N L cond_mode marginal_term S states K n" (`head`), then one line per rank of Hansel.viterbi_kbest's dict
+    `res`: the rank, ll_chain, gap, hamming0, the i_0 of the nearest recovered haplotype and the number of SNPs at which they differ
+    (-1 and -1 where nothing was recovered), and the SNP string.  `per_rank` is kbest_of's dict for `res` against the recovered
+    haplotypes in out.fasta's order, `i0s` their i_0s."""
+    lines = ["# %d\t%d\t%s\t%d\t%d\t%d\t%d\t%d\n" % tuple(head)]
+    for q in range(res["n"]):
+        near = int(per_rank["nearest"][q])
+        lines.append("%d\t%.6f\t%.6f\t%d\t%d\t%d\t%s\n" % (
+            q, res["ll_chain"][q], per_rank["gap"][q], int(per_rank["hamming0"][q]), int(i0s[near]) if near >= 0 else -1,
+            int(per_rank["distance"][q]), Hansel.path_str(res["paths"][q][1:])))
+    return "".join(lines)
+
+
+def write_kbest(paths, unweighted, vcf_h, args):
+    """--kbest: the K best haplotypes of the copy taken before the spins, set beside the distinct recovered haplotypes in
+    out.fasta's order.  A window the library refuses (too many states, or K lists of them too many slots) or a hole: a note on
+    stderr and no file."""
+    from .hansel import kbest_of
+    try:
+        res = unweighted.viterbi_kbest(args.kbest)
+    except GretelHipError as e:
+        sys.stderr.write("[NOTE] --kbest: %s\n" % e)
+        return
+    if res["hole_at"]:
+        sys.stderr.write("[NOTE] --kbest: no candidate at SNP %d, no k-best haplotypes\n" % res["hole_at"])
+        return
+    keys = sorted(paths, key=lambda x: paths[x]["i_0"])
+    s, _, states, _ = unweighted.viterbi_info()
+    per_rank = kbest_of(res, _path_array(paths, keys, unweighted.n))
+    with open(args.out + "/gretel.kbest", "w") as fh:
+        fh.write(kbest_text(_score_head(unweighted, vcf_h) + (s, states, args.kbest, res["n"]), res, per_rank, [paths[k]["i_0"] for k in keys]))
+
+
+def check_kbest_options(args):
+    """The refusal of --kbest (before any BAM read or GPU call): a message, or None."""
+    if args.kbest is not None and not 1 <= args.kbest <= KBEST_MAX:
+        return "--kbest must be 1..%d" % KBEST_MAX
+    return None
+
+
 def check_score_options(args):
     """The refusal of --known (before any BAM read or GPU call): a message, or None."""
     if args.known is None:
@@ -442,7 +493,7 @@ def check_exact_options(args):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    bad = check_assign_options(args) or check_score_options(args) or check_beam_options(args) or check_exact_options(args)
+    bad = check_assign_options(args) or check_score_options(args) or check_beam_options(args) or check_exact_options(args) or check_kbest_options(args)
     if bad:
         sys.stderr.write("[FAIL] %s\n" % bad)
         return 2
@@ -469,7 +520,7 @@ def main(argv=None):
                                 stepper="all" if args.pepper else "samtools", keep_reads=args.assign_reads)     # cmd.py:78
     hansel.snapshot_original()                                                    # cmd.py:79 (what the copy is used for)
     # (the reference's copy of cmd.py:79, made only where something is scored against the matrix as the reads filled it)
-    unweighted = hansel.copy() if (args.score_paths or args.known or args.margins) else None
+    unweighted = hansel.copy() if (args.score_paths or args.known or args.margins or args.kbest) else None
     if args.dumpmatrix:
         hansel.save_hansel_dump(args.dumpmatrix)                                  # cmd.py:81-82
     if gap_report(hansel, vcf_h):
@@ -496,6 +547,8 @@ def main(argv=None):
         write_known(paths, unweighted, vcf_h, args)
     if args.margins:
         write_margins(paths, unweighted, vcf_h, args)
+    if args.kbest:
+        write_kbest(paths, unweighted, vcf_h, args)
     try:                       # the decoder's kept working buffers (include/gretel_io.h: GIO_KEEP_MB): a run has one decode
         from . import bamio
         if getattr(bamio, "_io", None) is not None:

@@ -3450,6 +3450,8 @@ static int check_symbol_rows(const uint8_t *paths, int n_paths, size_t n1, int c
 #include "viterbi.hpp"
 // max-marginals of the chain likelihood: the decoder's forward walk with its scores kept, a backward walk, a parallel reduction
 #include "viterbi_marg.hpp"
+// k-best exact decoding: a ranked list of prefixes per state, merged by counting (gh_viterbi_kbest)
+#include "viterbi_kbest.hpp"
 // ... over every window of a batch or panel, the decoders of a round side by side: gh_panel_viterbi_spin, gh_viterbi_states
 #include "viterbi_panel.hpp"
 // ... and the max-marginals over every window: gh_panel_viterbi_marginals

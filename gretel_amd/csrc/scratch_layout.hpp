@@ -86,7 +86,7 @@ inline beam_bufs beam_layout(void *base, int N, size_t table_doubles, int width)
 struct vit_out {
     uint32_t U;        // k_vit_union
     int hole_at;       // k_vit_walk
-    int end_state;     // k_vit_trace
+    int end_state;     // k_vit_trace; k_vitk_trace: how many paths it returned
     int pad;
     double ll;         // k_vit_trace
 };
@@ -130,6 +130,29 @@ inline vitm_bufs vitm_layout(void *base, int N, size_t table_doubles, int states
     if (!states) return {out, nullptr, nullptr, nullptr, nullptr, nullptr, c.used};
     return {out, c.take<double>(table_doubles), c.take<double>((size_t)N * ns), c.take<uint8_t>(n1), c.take<double>(n1 * GH_NSYM), c.take<uint8_t>(n1),
             c.used};
+}
+
+// k-best decoding (viterbi_kbest.hpp), in the exact decoder's block of the handle, `out` first for the same reason.  A slot is
+// (state, rank), `states * k` of them (at most GH_VITERBI_MAX_STATES): one back-pointer byte per position and slot, the end lists
+// (scores per slot, a count per state), and what goes home: k path rows, k scores and how many of them are filled.
+struct vitk_bufs {
+    vit_out *out;
+    double *Gb;
+    uint8_t *bp;           // [N + 1][states][k] and four bytes more: k_vitk_trace copies whole words
+    double *vend;          // [states][k]
+    uint8_t *cend;         // [states] entries a state holds at p = N, 0 = not reachable
+    uint8_t *paths;        // [k][N + 1]
+    double *ll;            // [k]
+    int32_t *n_out;
+    size_t total;
+};
+
+inline vitk_bufs vitk_layout(void *base, int N, size_t table_doubles, int states, int k)
+{
+    scratch_carver c{(char *)base};
+    const size_t n1 = (size_t)N + 1, ns = (size_t)states, nk = (size_t)k;
+    return {c.take<vit_out>(1), c.take<double>(table_doubles), c.take<uint8_t>(n1 * ns * nk + 4), c.take<double>(ns * nk), c.take<uint8_t>(ns),
+            c.take<uint8_t>(nk * n1), c.take<double>(nk), c.take<int32_t>(1), c.used};
 }
 
 // the exact decoder over a panel (viterbi_panel.hpp), a block of the batch: one descriptor per window (WD = vit_win, which holds

@@ -121,6 +121,39 @@ def margins_of(mm, cm, paths, cand_order="ACGT-"):
                 n_best=(x[:, 1:] == best[None, 1:]).sum(axis=1).astype(np.int32))
 
 
+def kbest_of(res, recovered=None):
+    """What Hansel.viterbi_kbest()'s dict `res` says per rank.  Host only, no handle.  Returns a dict of arrays with one entry per
+    returned path:
+      gap float64[n]       ll_chain[0] - ll_chain[i]: what rank i lacks to the best (0.0 where both are -inf);
+      hamming0 int32[n]    the SNPs at which it differs from rank 0: a near-tie flipped at one SNP, or another sequence;
+    and with `recovered` (uint8[H][N+1], the haplotypes a run recovered):
+      nearest int32[n]     the row of `recovered` that differs from it at the fewest SNPs, the first of them at a tie;
+      distance int32[n]    at how many SNPs -- 0 means it IS that haplotype.  Both are -1 where H = 0."""
+    x = np.asarray(res["paths"], dtype=np.uint8)
+    ll = np.asarray(res["ll_chain"], dtype=np.float64)
+    n = len(ll)
+    if x.ndim != 2 or len(x) != n:
+        raise ValueError("kbest_of: paths must be [n][N+1] and ll_chain [n] (got %s, %s)" % (x.shape, ll.shape))
+    gap = np.zeros(n)
+    for i in range(n):
+        gap[i] = 0.0 if ll[i] == ll[0] else ll[0] - ll[i]
+    out = dict(gap=gap, hamming0=(x[:, 1:] != x[:1, 1:]).sum(axis=1).astype(np.int32))
+    if recovered is not None:
+        rec = np.asarray(recovered, dtype=np.uint8)
+        if rec.ndim == 1:
+            rec = rec.reshape(1, -1) if rec.size else rec.reshape(0, x.shape[1])
+        if rec.ndim != 2 or rec.shape[1] != x.shape[1]:
+            raise ValueError("kbest_of: recovered must be [H][N+1] with N+1 = %d (got %s)" % (x.shape[1], rec.shape))
+        near = np.full(n, -1, dtype=np.int32)
+        dist = np.full(n, -1, dtype=np.int32)
+        if len(rec) and n:
+            d = (x[:, None, 1:] != rec[None, :, 1:]).sum(axis=2)
+            near = d.argmin(axis=1).astype(np.int32)                 # (argmin: the first of equals)
+            dist = d[np.arange(n), near].astype(np.int32)
+        out.update(nearest=near, distance=dist)
+    return out
+
+
 class Hansel:
     def __init__(self, n_snps, band=None, storage="f32", cond_mode="A", marginal_term=False, device=-1,
                  cand_order="ACGT-", offer_zero=False):
@@ -494,6 +527,20 @@ class Hansel:
         if hole.value:
             return dict(mm=None, cm=None, hole_at=hole.value)
         return dict(mm=mm, cm=cm, hole_at=0)
+
+    def viterbi_kbest(self, k):
+        """The k full paths of largest chain likelihood on the tensor as it is now, exactly, best first (gh_viterbi_kbest; the
+        definition and the two tie orders: INTEGRATION.md "K-best decoding").  Returns dict(n, hole_at, paths uint8[n][N+1],
+        ll_chain float64[n]), n = min(k, the number of full paths); at a hole n = 0 and the arrays are empty.  Served for
+        1 <= k <= 32 where k * S^min(L, N) <= 4096; beyond that GretelHipError, whose message names the largest k the window
+        takes.  kbest_of() reads the result.  The tensor is not touched."""
+        self._ensure()
+        k = int(k)
+        paths = np.zeros((max(1, min(k, _lib.GH_KBEST_MAX)), self.n + 1), dtype=np.uint8)
+        ll = np.zeros(len(paths))
+        n, hole = C.c_int(), C.c_int()
+        check(self._lib.gh_viterbi_kbest(self._h, k, _p(paths), _p(ll), C.byref(n), C.byref(hole)))
+        return dict(n=n.value, hole_at=hole.value, paths=paths[:n.value], ll_chain=ll[:n.value])
 
     def viterbi_states(self):
         """(S, Le, states = S^Le) of the tensor as it stands, without decoding (gh_viterbi_states): what viterbi_path would need.

@@ -390,6 +390,40 @@ int gh_viterbi_states(gh_t *h, int64_t out[3]);
  * following gh_spin stay as they are, bit for bit.  gh_viterbi_info afterwards describes this call: S, Le, states, scratch bytes. */
 int gh_viterbi_marginals(gh_t *h, double *mm /*[N+1][7]*/, uint8_t *cm /*[N+1]*/, int *hole_at);
 
+/* K-best exact decoding of the chain likelihood (no reference counterpart; INTEGRATION.md "K-best decoding").  gh_viterbi_path says
+ * what the best full path is and gh_viterbi_marginals how much every other choice would cost; this returns the runner-up paths
+ * themselves: the k full paths of largest score, exactly.  Notation as in "Exact decoding" above; a state at p is the last
+ * min(Le, p) picks.
+ *   Per state.  Every state keeps a list of at most k prefixes in rank order 0, 1, ...  At p = 0 there is the empty state with one
+ *   prefix of score +0.0.  At step p every kept prefix of rank r in predecessor state s' spawns one child per c in cm(p), of score
+ *   score + w_p(c | s'), the additions those of the exact decoder: V + (prefix + T_Le) with prefix the marginal term and then lags
+ *   1 .. Le-1, and V + prefix alone for p < Le.
+ *   Merge.  For p > Le the children that meet in a state differ at x[p-Le] or in r.  They stand in the total order (1) score
+ *   descending, by plain IEEE > and ==; (2) q(x[p-Le]) ascending; (3) r ascending; the first min(k, #children) are kept as ranks
+ *   0, 1, ...  For p <= Le a state has one predecessor, whose list carries over in order (and has exactly one entry).
+ *   End.  The entries of all states at p = N stand in the order (1) score descending; (2) ascending lexicographic
+ *   (q(x[N]), ..., q(x[N-Le+1])); (3) r ascending.  The first n_out = min(k, number of full paths) are returned in that order:
+ *   paths_out[i][0] = '_' (6), ll_chain[i] = the path's sequential sum from +0.0 in ascending p.
+ *   Exactness.  fl(a + w) is monotone in a, so a child of a prefix outside the k best of its state is preceded by the k children
+ *   of those that take the same pick: it is never among the k best of the state it enters.  By induction the k lists at p = N
+ *   hold the k largest scores.  Hence:
+ *     ll_chain[0..n_out) is, as a list, the n_out largest values of score(x) over all full paths, bit for bit;
+ *     ll_chain[i] == gh_score_paths(paths_out[i]).ll_chain with n_on == N;  the paths are pairwise distinct;
+ *     k = 1 is gh_viterbi_path, path and score;  max_c mm[N][c] of gh_viterbi_marginals == ll_chain[0];
+ *     -inf is a score like any other (reachability is a count per state, never a score).
+ *   Hole: at the first p with empty cm(p), hole_at = p, n_out = 0 and nothing else is written.  Otherwise hole_at = 0.
+ *   Limits: 1 <= k <= GH_KBEST_MAX (a back-pointer is one byte: the dropped digit in 3 bits, the predecessor's rank in 5) and
+ *   k * S^Le <= GH_VITERBI_MAX_STATES: the lists are the exact decoder's two score rows (64 KB on chip).
+ * GH_ERR_ARG for a null argument (ll_chain included), k outside 1..GH_KBEST_MAX, offer_zero, more than GH_VITERBI_MAX_STATES
+ * states (gh_viterbi_path's message) or k * S^Le beyond it (the message names S, Le, the states and the largest k the window
+ * takes, GH_VITERBI_MAX_STATES / states).  GH_ERR_STATE before any fill.  GH_ERR_NOMEM names the size of the scratch: the exact
+ * decoder's block of the handle, here the table, (N + 1) * S^Le * k back-pointer bytes (at most (N + 1) * 4096), the end lists
+ * and the k path rows.
+ * It only reads the tensor: the band, L, the fill statistics, the snapshot, the handle's conditional tables and the results of a
+ * following gh_spin stay as they are, bit for bit.  gh_viterbi_info afterwards describes this call: S, Le, states = S^Le, bytes. */
+#define GH_KBEST_MAX 32
+int gh_viterbi_kbest(gh_t *h, int k, uint8_t *paths_out /*[k][N+1]*/, double *ll_chain /*[k]*/, int *n_out, int *hole_at);
+
 /* gh_viterbi_spin over every window of a batch or panel, the decoders of a round side by side: a window's exact decoder is ONE
  * workgroup, so one launch with a workgroup per window decodes all of them in about the time of the slowest.
  * Window w's paths ([max_paths][N_w + 1] at paths_out + paths_off[w], as gh_panel_spin; for a batch paths_off[w] =
