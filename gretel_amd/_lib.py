@@ -169,6 +169,8 @@ def load():
         "gh_panel_viterbi_info": [vp, vp],
         "gh_panel_viterbi_marginals": [vp, vp, vp, vp, vp],
         "gh_panel_viterbi_marginals_info": [vp, vp],
+        "gh_panel_viterbi_kbest": [vp, vp, vp, vp, vp, vp, vp, vp],
+        "gh_panel_viterbi_kbest_info": [vp, vp],
         "gh_debug_panel_viterbi_phases": [i32, vp],
         "gh_coverage_sites": [i32, vp, vp, vp, i64, C.c_int32, C.c_int32, C.c_int32, vp, vp],
     }

@@ -53,6 +53,9 @@ KBEST_MAX = 32             # include/gretel_hip.h: GH_KBEST_MAX
 MARGINS_HELP = ("compute the max-marginals of the chain likelihood on the unreweighted matrix (per SNP and allele the best likelihood "
                 "of any haplotype that takes it; the state limit of --exact applies) and write per-SNP confidence gaps and "
                 "per-haplotype regrets to gretel.margins")          # (gretel_amd.panel's --margins says the same)
+KBEST_HELP = ("find the K exactly best haplotypes of the chain likelihood on the unreweighted matrix (1..%d; K times the states of "
+              "--exact must not exceed %d) and write them, their gaps and the nearest recovered haplotype to gretel.kbest"
+              % (KBEST_MAX, EXACT_MAX_STATES))               # (gretel_amd.panel's --kbest says the same)
 
 
 def build_parser():
@@ -85,9 +88,7 @@ def build_parser():
                    "decoding over S^min(L, N) states, at most %d: L <= 6 without deletion columns, L <= 5 with them) instead of "
                    "the greedy walk" % EXACT_MAX_STATES)
     p.add_argument("--margins", action="store_true", help=MARGINS_HELP)
-    p.add_argument("--kbest", type=int, default=None, metavar="K", help="find the K exactly best haplotypes of the chain likelihood on "
-                   "the unreweighted matrix (1..%d; K times the states of --exact must not exceed %d) and write them, their gaps "
-                   "and the nearest recovered haplotype to gretel.kbest" % (KBEST_MAX, EXACT_MAX_STATES))
+    p.add_argument("--kbest", type=int, default=None, metavar="K", help=KBEST_HELP)
     p.add_argument("--version", action="version", version="%(prog)s " + __version__)
     return p
 
@@ -414,24 +415,32 @@ def kbest_text(head, res, per_rank, i0s):
     return "".join(lines)
 
 
+def write_kbest_result(paths, res, head, vcf_h, args, name=None):
+    """What follows the k-best call, for this CLI and for gretel_amd.panel (which makes one call for all its regions): `res` is
+    Hansel.viterbi_kbest's dict, `head` the header's first seven figures (N, L, cond_mode, marginal_term, S, states -- S and states
+    as the call left them -- and K).  At a hole the note on stderr (behind `name` where there is one) and no file; otherwise
+    gretel.kbest, the ranks set beside the distinct recovered haplotypes in out.fasta's order."""
+    from .hansel import kbest_of
+    if res["hole_at"]:
+        sys.stderr.write("%s[NOTE] --kbest: no candidate at SNP %d, no k-best haplotypes\n" % ("%s: " % name if name else "", res["hole_at"]))
+        return
+    keys = sorted(paths, key=lambda x: paths[x]["i_0"])
+    per_rank = kbest_of(res, _path_array(paths, keys, res["paths"].shape[1] - 1))
+    with open(args.out + "/gretel.kbest", "w") as fh:
+        fh.write(kbest_text(tuple(head) + (res["n"],), res, per_rank, [paths[k]["i_0"] for k in keys]))
+
+
 def write_kbest(paths, unweighted, vcf_h, args):
     """--kbest: the K best haplotypes of the copy taken before the spins, set beside the distinct recovered haplotypes in
     out.fasta's order.  A window the library refuses (too many states, or K lists of them too many slots) or a hole: a note on
     stderr and no file."""
-    from .hansel import kbest_of
     try:
         res = unweighted.viterbi_kbest(args.kbest)
     except GretelHipError as e:
         sys.stderr.write("[NOTE] --kbest: %s\n" % e)
         return
-    if res["hole_at"]:
-        sys.stderr.write("[NOTE] --kbest: no candidate at SNP %d, no k-best haplotypes\n" % res["hole_at"])
-        return
-    keys = sorted(paths, key=lambda x: paths[x]["i_0"])
     s, _, states, _ = unweighted.viterbi_info()
-    per_rank = kbest_of(res, _path_array(paths, keys, unweighted.n))
-    with open(args.out + "/gretel.kbest", "w") as fh:
-        fh.write(kbest_text(_score_head(unweighted, vcf_h) + (s, states, args.kbest, res["n"]), res, per_rank, [paths[k]["i_0"] for k in keys]))
+    write_kbest_result(paths, res, _score_head(unweighted, vcf_h) + (s, states, args.kbest), vcf_h, args)
 
 
 def check_kbest_options(args):

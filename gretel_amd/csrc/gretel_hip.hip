@@ -2417,6 +2417,7 @@ struct gh_batch {
     std::vector<hipEvent_t> vit_ev;
     int64_t vit_info[4];
     int64_t vitm_info[4];       // gh_panel_viterbi_marginals_info (viterbi_marg_panel.hpp: the same block and events)
+    int64_t vitk_info[4];       // gh_panel_viterbi_kbest_info (viterbi_kbest_panel.hpp: likewise)
 };
 
 extern "C" int gh_batch_destroy(gh_batch_t *b)
@@ -3456,3 +3457,5 @@ static int check_symbol_rows(const uint8_t *paths, int n_paths, size_t n1, int c
 #include "viterbi_panel.hpp"
 // ... and the max-marginals over every window: gh_panel_viterbi_marginals
 #include "viterbi_marg_panel.hpp"
+// ... and the k best haplotypes of every window: gh_panel_viterbi_kbest
+#include "viterbi_kbest_panel.hpp"

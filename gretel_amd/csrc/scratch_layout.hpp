@@ -190,3 +190,24 @@ template <typename WD> inline vitm_panel_bufs<WD> vitm_panel_layout(void *base, 
     return {c.take<WD>((size_t)n), c.take<int32_t>(2 * (size_t)n), c.take<vit_out>((size_t)n), c.take<double>(positions * GH_NSYM),
             c.take<uint8_t>(positions), c.used};
 }
+
+// k-best decoding over a panel (viterbi_kbest_panel.hpp), in the same block of the batch: one descriptor per window in window
+// order (WD = vitk_win), the two walk launches' lists (window indices: the walks with the table ring from the front of the n ints,
+// those without behind them), the windows' vit_outs gathered for one copy to the host, and their path rows and scores gathered
+// back to back in window order (`path_bytes` = the sum of k_w * (N_w + 1), `scores` = the sum of k_w: window w's rows at the
+// sum of k_v * (N_v + 1) before it, its scores at the sum of k_v before it)
+template <typename WD> struct vitk_panel_bufs {
+    WD *wd;
+    int32_t *list;         // [n]
+    vit_out *outs;         // [n]
+    uint8_t *paths;        // [path_bytes]
+    double *ll;            // [scores]
+    size_t total;
+};
+
+template <typename WD> inline vitk_panel_bufs<WD> vitk_panel_layout(void *base, int n, size_t path_bytes, size_t scores)
+{
+    scratch_carver c{(char *)base};
+    return {c.take<WD>((size_t)n), c.take<int32_t>((size_t)n), c.take<vit_out>((size_t)n), c.take<uint8_t>(path_bytes), c.take<double>(scores),
+            c.used};
+}

@@ -542,6 +542,14 @@ class Hansel:
         check(self._lib.gh_viterbi_kbest(self._h, k, _p(paths), _p(ll), C.byref(n), C.byref(hole)))
         return dict(n=n.value, hole_at=hole.value, paths=paths[:n.value], ll_chain=ll[:n.value])
 
+    def viterbi_kbest_max(self):
+        """The largest k viterbi_kbest() takes on the tensor as it stands: min(32, 4096 // states) from viterbi_states(), and 0
+        where the window is beyond the exact decoder's cap (or offers nothing anywhere).  Host arithmetic over that call."""
+        states = self.viterbi_states()[2]
+        if states < 1 or states > _lib.GH_VITERBI_MAX_STATES:
+            return 0
+        return min(_lib.GH_KBEST_MAX, _lib.GH_VITERBI_MAX_STATES // states)
+
     def viterbi_states(self):
         """(S, Le, states = S^Le) of the tensor as it stands, without decoding (gh_viterbi_states): what viterbi_path would need.
         The count is given however large it is (it saturates at 2^63 - 1); the decoder serves up to 4096."""
@@ -912,6 +920,48 @@ class HanselBatch:
         launches -- forward and backward together --, scratch bytes summed over the handles' blocks)."""
         out = np.zeros(4, dtype=np.int64)
         check(self._lib.gh_panel_viterbi_marginals_info(self._b, _p(out)))
+        return tuple(int(v) for v in out)
+
+
+    def viterbi_kbest(self, k):
+        """Hansel.viterbi_kbest over every window, the walks side by side in one launch and the traces in another
+        (gh_panel_viterbi_kbest).  k: an int for all windows, or a sequence with one entry per window (regions differ in their
+        states, so the largest k they take differs: Hansel.viterbi_kbest_max()).  One dict per window, shaped as
+        Hansel.viterbi_kbest's: n, hole_at, paths uint8[n][n_snps + 1], ll_chain float64[n]; each window gets its own arrays, each
+        the result of that call on the window alone.  The tensors are not touched.  A window the single call would refuse (too
+        many states, or k lists of them too many slots) refuses the whole call before anything is touched (GretelHipError names
+        the window).  The scratch is the sum of the windows' (N + 1) * states * k bytes and their tables."""
+        n = len(self.hansels)
+        try:
+            ks = [int(k)] * n
+        except TypeError:
+            ks = [int(v) for v in k]
+            if len(ks) != n:
+                raise ValueError("viterbi_kbest: k has %d entries for %d windows" % (len(ks), n))
+        ka = np.asarray(ks, dtype=np.int32)
+        # (room for what a refused k would ask is not needed: the call refuses before it writes)
+        room = np.clip(ka, 1, _lib.GH_KBEST_MAX).astype(np.int64)
+        n1s = np.asarray([h.n + 1 for h in self.hansels], dtype=np.int64)
+        poff = np.zeros(n, dtype=np.int64)
+        poff[1:] = np.cumsum((room * n1s)[:-1])
+        loff = np.zeros(n, dtype=np.int64)
+        loff[1:] = np.cumsum(room[:-1])
+        paths = np.zeros(int((room * n1s).sum()), dtype=np.uint8)
+        ll = np.zeros(int(room.sum()))
+        n_out = np.zeros(n, dtype=np.int32)
+        hole = np.zeros(n, dtype=np.int32)
+        check(self._lib.gh_panel_viterbi_kbest(self._b, _p(ka), _p(paths), _p(poff), _p(ll), _p(loff), _p(n_out), _p(hole)))
+        out = []
+        for w in range(n):
+            m, n1, a, e = int(n_out[w]), int(n1s[w]), int(poff[w]), int(loff[w])
+            out.append(dict(n=m, hole_at=int(hole[w]), paths=paths[a:a + m * n1].reshape(m, n1).copy(), ll_chain=ll[e:e + m].copy()))
+        return out
+
+    def viterbi_kbest_info(self):
+        """The last viterbi_kbest() of this batch (gh_panel_viterbi_kbest_info): (windows, windows that met a hole, walk launches,
+        scratch bytes summed over the handles' blocks)."""
+        out = np.zeros(4, dtype=np.int64)
+        check(self._lib.gh_panel_viterbi_kbest_info(self._b, _p(out)))
         return tuple(int(v) for v in out)
 
 

@@ -16,6 +16,11 @@ recovered haplotype scored against a copy of the region's matrix taken before th
 --margins writes OUT/<name>/gretel.margins, the max-marginals of the region's matrix before the spins, all regions' walks side
 by side (HanselPanel.viterbi_marginals); without --exact a region beyond the decoder's cap gets the library's message as a
 [NOTE] behind its name and no such file, its other files are written and the exit status is unaffected.
+--kbest K writes OUT/<name>/gretel.kbest, the K exactly best haplotypes of the region's matrix before the spins set beside the
+recovered ones, all regions' walks side by side in one call made before the spins (HanselPanel.viterbi_kbest), with the greedy
+spin or --exact, with or without --margins; a region the library would refuse (too many states, or K lists of them more slots
+than the decoder holds) gets the library's message as a [NOTE] behind its name and no such file, a region that met a hole gets
+the single CLI's note behind its name; the other files are written and the exit status is unaffected.
 --beam and --known are the single CLI's alone: a panel offers neither.
 A region gretel cannot recover (a SNP without pairwise evidence, or no read that carries two SNPs) gets gretel's [FAIL] text on
 stderr behind its name and is left out; the exit status is then 1, once every other region has been written.  Stdout: one line
@@ -55,6 +60,7 @@ def build_parser():
                    "decoding over S^min(L, N) states, at most %d), the regions' decoders side by side, instead of the greedy walk"
                    % cmd.EXACT_MAX_STATES)
     p.add_argument("--margins", action="store_true", help=cmd.MARGINS_HELP)
+    p.add_argument("--kbest", type=int, default=None, metavar="K", help=cmd.KBEST_HELP)
     p.add_argument("--version", action="version", version="%(prog)s " + __version__)
     return p
 
@@ -77,7 +83,7 @@ def main(argv=None):
     if args.paths < 1:
         sys.stderr.write("[FAIL] -p/--paths must be at least 1\n")
         return 2
-    bad = cmd.check_assign_options(args)
+    bad = cmd.check_assign_options(args) or cmd.check_kbest_options(args)
     if bad:
         sys.stderr.write("[FAIL] %s\n" % bad)
         return 2
@@ -86,6 +92,7 @@ def main(argv=None):
     stepper = "all" if args.pepper else "samtools"
     kept = []                   # (region, vcf_h, hansel, the copy --score-paths scores against or None)
     served = []                 # --margins: indices into kept of the regions the max-marginals serve
+    ranked = []                 # --kbest: likewise for the k-best decoding
     failed = 0
     for k, (r, vh) in enumerate(zip(regions, vcfs)):
         hansel = None
@@ -128,6 +135,17 @@ def main(argv=None):
                 margins_ok = False
         if args.margins and margins_ok:
             served.append(len(kept))
+        if args.kbest:                          # (asked beforehand: one region the library refuses would refuse the whole call)
+            kbest_ok = True
+            try:
+                states = hansel.viterbi_states()[2]
+                if states > cmd.EXACT_MAX_STATES or states * args.kbest > cmd.EXACT_MAX_STATES:
+                    hansel.viterbi_kbest(args.kbest)    # (raises: the library's own message)
+            except GretelHipError as e:
+                _fail(r["name"], "[NOTE] --kbest: %s\n" % e)
+                kbest_ok = False
+            if kbest_ok:
+                ranked.append(len(kept))
         kept.append((r, vh, hansel, hansel.copy() if args.score_paths else None))       # (as gretel_amd.cmd: before the spins)
     margins = {}                # index into kept -> (viterbi_marginals' dict, the header's figures), taken before the spins
     if served:
@@ -136,6 +154,12 @@ def main(argv=None):
         for k, h, res in zip(served, hs, HanselPanel(hs).viterbi_marginals()):
             s, _, states, _ = h.viterbi_info()
             margins[k] = (res, cmd._score_head(h, kept[k][1]) + (s, states))
+    kbest = {}                  # index into kept -> (viterbi_kbest's dict, the header's figures), likewise
+    if ranked:
+        hs = [kept[k][2] for k in ranked]
+        for k, h, res in zip(ranked, hs, HanselPanel(hs).viterbi_kbest(args.kbest)):
+            s, _, states, _ = h.viterbi_info()
+            kbest[k] = (res, cmd._score_head(h, kept[k][1]) + (s, states, args.kbest))
     if kept:
         panel = HanselPanel([h for _, _, h, _ in kept])
         results = panel.viterbi_spin(args.paths, cmd.MIN_REMOVE) if args.exact else panel.spin(args.paths, cmd.MIN_REMOVE)
@@ -154,6 +178,8 @@ def main(argv=None):
                     cmd.write_scores(paths, unweighted, vh, ns)
                 if k in margins:
                     cmd.write_margins_result(paths, margins[k][0], margins[k][1], hansel._cfg["cand_order"], vh, ns, name=r["name"])
+                if k in kbest:
+                    cmd.write_kbest_result(paths, kbest[k][0], kbest[k][1], vh, ns, name=r["name"])
                 sys.stdout.write("%s\t%d\t%d\t%d\t%d\n" % (r["name"], vh["N"], hansel.L, res["n"], len(paths)))
     try:                        # (the decoder's kept working buffers: see gretel_amd.cmd)
         from . import bamio

@@ -490,6 +490,44 @@ int gh_debug_panel_viterbi_phases(int on, double out[4]);
 int gh_panel_viterbi_marginals(gh_batch_t *b, double *mm, uint8_t *cm, const int64_t *pos_off /*[n]*/, int *hole_at /*[n]*/);
 int gh_panel_viterbi_marginals_info(gh_batch_t *b, int64_t out[4]);
 
+/* gh_viterbi_kbest over every window of a batch or panel, each with its own k (regions of a panel differ in S^Le, so the largest
+ * k they take differs), the walks side by side: a window's k-best walk and its trace are ONE workgroup each, so one launch with a
+ * workgroup per window does every window's in about the time of the slowest.
+ * Window w's n_out[w] path rows ([N_w + 1] bytes each, from paths_out + paths_off[w]; paths_off in bytes), its scores (from
+ * ll_chain + ll_off[w]; ll_off in doubles), n_out[w] and hole_at[w] are what gh_viterbi_kbest(h_w, k[w], ...) writes for that handle
+ * alone, bit for bit and in the same order, the two tie orders and -inf scores included.  Rows and scores beyond n_out[w] are not
+ * written; nothing of a window that met a hole is written (n_out[w] = 0, the others run on).  The running sums of
+ * k[w] * (N_w + 1) and of k[w] pack the windows back to back.
+ * Afterwards each handle's gh_viterbi_info is what the single call leaves (S, Le, states, the bytes of that window's block).  The
+ * call only reads the tensors: for every window the band, L, the fill statistics, the snapshot, the conditional tables and the
+ * results of a following gh_spin, gh_panel_spin or gh_panel_viterbi_spin stay as they are, bit for bit.
+ * Launches: the walks in one, and a second for the windows that walk without the table ring (one candidate symbol and Le > 12, or
+ * GH_VIT_STAGE=0) -- the single call's decision, window by window; K is a run-time value of the walk, so windows of differing k
+ * share a launch; the traces in one; a gather of the vit_outs, the rows and the scores in window order, then the vit_outs home
+ * (the host learns n_out and the holes) and one copy each of rows and scores per run of neighbouring windows that are full
+ * (n_out[w] == k[w], no hole) and whose destinations lie as the gathered ranges do: three copies in all for a packed call with
+ * every window full.  No workgroup depends on another: a panel of more windows than the card holds workgroups finishes all the same.
+ * Scratch: each window's block is its handle's own exact-decoder block under the k-best layout, exactly as the single call
+ * reserves it (kept until gh_destroy); all blocks are reserved before the first walk is launched.  The panel asks for the sum over
+ * its windows of (N + 1) * states * k bytes plus the tables and the small parts.  GH_ERR_NOMEM names the window whose block could
+ * not be had and that sum.  The descriptors, the launch list and the gathered results are a block of the batch, shared with
+ * gh_panel_viterbi_spin and gh_panel_viterbi_marginals.
+ * Stream order: a window's marginal tables and chain table on its handle's stream, an event per window before the batch's
+ * stream, everything panel-wide on the batch's stream; the host waits for the batch's stream before it touches a handle.
+ * Refusals are made as a whole, before any window's scratch or gh_viterbi_info is touched: GH_ERR_ARG for a null argument, a
+ * negative offset, a k[w] outside 1..GH_KBEST_MAX, a window with offer_zero, a window with more than GH_VITERBI_MAX_STATES states
+ * or one whose k[w] * states is beyond it (gh_viterbi_kbest's messages behind "window <w>: "; the last names the largest k the
+ * window takes); GH_ERR_STATE for a window never filled.
+ * gh_panel_viterbi_kbest_info, the last such call: out[0] = windows, out[1] = windows that met a hole, out[2] = walk launches,
+ * out[3] = scratch bytes summed over the handles' blocks.  GH_ERR_ARG for a null argument.
+ * Under gh_debug_panel_viterbi_phases (measurements only) this call adds up too: [0] the preamble and the table builds, [1] the
+ * walks, [2] the traces, [3] the gather and the copies home. */
+int gh_panel_viterbi_kbest(gh_batch_t *b, const int *k /*[n]*/,
+                           uint8_t *paths_out, const int64_t *paths_off /*[n], bytes*/,
+                           double *ll_chain,  const int64_t *ll_off    /*[n], doubles*/,
+                           int *n_out /*[n]*/, int *hole_at /*[n]*/);
+int gh_panel_viterbi_kbest_info(gh_batch_t *b, int64_t out[4]);
+
 /* tensor export/import for --dumpmatrix (gretel/cmd.py:81-82) and tests:
  * band layout [(N+2)][band][7][7] as doubles; dense layout [7][7][N+2][N+2] (gretel/cmd.py:76-77). */
 int gh_export_band(gh_t *h, double *out);
