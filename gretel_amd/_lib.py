@@ -19,6 +19,7 @@ GH_COND = {"A": 0, "B": 1, "C": 2, "D": 3, "E": 4}
 GH_BEAM_MAX = 32
 GH_VITERBI_MAX_STATES = 4096
 GH_KBEST_MAX = 32
+GH_MASKED_MAX_SETS = 256
 GH_K = {"fill": 0, "marg": 1, "lt": 2, "walk": 3, "reweight": 4, "seg": 5, "rwseg": 6}
 GH_FLOW = {0: "none", 1: "serial", 2: "seg", 3: "rwseg", 4: "fuse", 5: "pools"}      # gh_spin_plan.flow
 GH_WALK = {"seg": 0, "spec": 1, "spec1": 2, "src": 3}                                # gh_spin_plan_in.walk_mode
@@ -165,6 +166,8 @@ def load():
         "gh_viterbi_states": [vp, vp],
         "gh_viterbi_marginals": [vp, vp, vp, P(i32)],
         "gh_viterbi_kbest": [vp, i32, vp, vp, P(i32), P(i32)],
+        "gh_viterbi_path_masked": [vp, vp, i32, vp, vp, vp],
+        "gh_viterbi_masked_info": [vp, vp],
         "gh_panel_viterbi_spin": [vp, i32, dbl, vp, vp, vp, vp, vp, vp],
         "gh_panel_viterbi_info": [vp, vp],
         "gh_panel_viterbi_marginals": [vp, vp, vp, vp, vp],

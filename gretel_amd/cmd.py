@@ -30,6 +30,16 @@ and, with --kbest K (INTEGRATION.md "K-best decoding"), against the matrix as it
                           nearest recovered haplotype, the number of SNPs at which they differ, and the SNP string; nothing where
                           K lists of the window's states do not fit 4096 slots or at a hole (a note on stderr, the run goes on)
 
+and, with --alternatives M and/or --pin SPEC (INTEGRATION.md "Constrained decoding"), against the matrix as it was before any
+reweighting:
+    <out>/gretel.alternatives  "# N L cond_mode marginal_term S states M n", a "B" line for the free best haplotype of the chain
+                          likelihood, one "A" line per alternative -- for the M SNPs of smallest max-marginal gap the exactly best
+                          haplotype that carries the runner-up allele there: SNP rank, genomic position, best and alternative allele,
+                          gap, its ll_chain, ll_best - ll, the SNPs at which it differs from the free best with the first and last
+                          of them (how far the flip reaches), the nearest recovered haplotype and its distance, the SNP string --
+                          and one "P" line per --pin (its index, the pinned sites, the same columns from ll_chain on); nothing
+                          where the window has more than 4096 states or a hole (a note on stderr, the run goes on)
+
 and, with --score-paths / --known FASTA (INTEGRATION.md "Scoring haplotypes"), against the matrix as it was before any reweighting:
     <out>/gretel.scores   "# N L cond_mode marginal_term" + one line per recovered haplotype: i_0, ll_chain, hp_original, n_greedy,
                           n_on, first_off, min_margin, argmin_margin and the genomic position of argmin_margin
@@ -50,6 +60,7 @@ MIN_REMOVE = 0.01          # cmd.py:157
 BEAM_MAX = 32              # include/gretel_hip.h: GH_BEAM_MAX
 EXACT_MAX_STATES = 4096    # include/gretel_hip.h: GH_VITERBI_MAX_STATES
 KBEST_MAX = 32             # include/gretel_hip.h: GH_KBEST_MAX
+MASKED_MAX = 255           # include/gretel_hip.h: GH_MASKED_MAX_SETS less the free best path, which is set 0 of the call
 MARGINS_HELP = ("compute the max-marginals of the chain likelihood on the unreweighted matrix (per SNP and allele the best likelihood "
                 "of any haplotype that takes it; the state limit of --exact applies) and write per-SNP confidence gaps and "
                 "per-haplotype regrets to gretel.margins")          # (gretel_amd.panel's --margins says the same)
@@ -89,6 +100,13 @@ def build_parser():
                    "the greedy walk" % EXACT_MAX_STATES)
     p.add_argument("--margins", action="store_true", help=MARGINS_HELP)
     p.add_argument("--kbest", type=int, default=None, metavar="K", help=KBEST_HELP)
+    p.add_argument("--alternatives", type=int, default=None, metavar="M", help="for the M SNPs whose call is least certain (smallest "
+                   "max-marginal gap) decode the best haplotype that carries the runner-up allele there, exactly, on the unreweighted "
+                   "matrix (1..%d; the state limit of --exact applies), and write them beside the free best haplotype to "
+                   "gretel.alternatives" % MASKED_MAX)
+    p.add_argument("--pin", action="append", default=None, metavar="SPEC", help="decode the best haplotype under constraints, exactly: "
+                   "SPEC = POS:ALLELES[,POS:ALLELES...], POS a 1-based genomic position that is a SNP of the window, ALLELES the "
+                   "alleles of ACGT- allowed there; repeatable, each use is one more line of gretel.alternatives")
     p.add_argument("--version", action="version", version="%(prog)s " + __version__)
     return p
 
@@ -389,16 +407,144 @@ def write_margins_result(paths, res, head, order, vcf_h, args, name=None):
         fh.write(margins_text(head, [paths[k]["i_0"] for k in keys], marg, res["mm"], res["cm"], vcf_h["snp_rev"]))
 
 
-def write_margins(paths, unweighted, vcf_h, args):
-    """--margins: the max-marginals of the copy taken before the spins, read for the distinct haplotypes in out.fasta's order.
-    A window beyond the exact decoder's cap: the library's message on stderr and no file."""
+def marginals_once(unweighted):
+    """The one max-marginals call --margins and --alternatives share: (Hansel.viterbi_marginals' dict, (S, states) as the call
+    left them), or (None, the library's refusal)."""
     try:
         res = unweighted.viterbi_marginals()
     except GretelHipError as e:
-        sys.stderr.write("[NOTE] --margins: %s\n" % e)
-        return
+        return None, e
     s, _, states, _ = unweighted.viterbi_info()
-    write_margins_result(paths, res, _score_head(unweighted, vcf_h) + (s, states), unweighted._cfg["cand_order"], vcf_h, args)
+    return res, (s, states)
+
+
+def write_margins(paths, unweighted, vcf_h, args, call=None):
+    """--margins: the max-marginals of the copy taken before the spins, read for the distinct haplotypes in out.fasta's order.
+    A window beyond the exact decoder's cap: the library's message on stderr and no file.  `call`: marginals_once's pair where
+    the call has been made already."""
+    res, info = call if call is not None else marginals_once(unweighted)
+    if res is None:
+        sys.stderr.write("[NOTE] --margins: %s\n" % info)
+        return
+    write_margins_result(paths, res, _score_head(unweighted, vcf_h) + info, unweighted._cfg["cand_order"], vcf_h, args)
+
+
+def parse_pin(spec):
+    """--pin SPEC -> [(genomic position, alleles)], or a message (a str) where the syntax is wrong."""
+    out, seen = [], set()
+    for part in spec.split(","):
+        pos, sep, alleles = part.partition(":")
+        if not sep or not pos.strip().isdigit() or not alleles or any(c not in "ACGT-" for c in alleles):
+            return "--pin %s: %r is not POS:ALLELES (POS a position, ALLELES a non-empty string over ACGT-)" % (spec, part)
+        if int(pos) in seen:
+            return "--pin %s: position %d is given twice" % (spec, int(pos))
+        seen.add(int(pos))
+        out.append((int(pos), alleles))
+    return out
+
+
+def check_masked_options(args):
+    """The refusals of --alternatives and --pin (before any BAM read or GPU call): a message, or None."""
+    if args.alternatives is not None and not 1 <= args.alternatives <= MASKED_MAX:
+        return "--alternatives must be 1..%d" % MASKED_MAX
+    for spec in args.pin or []:
+        pins = parse_pin(spec)
+        if isinstance(pins, str):
+            return pins
+    if (args.alternatives or 0) + len(args.pin or []) > MASKED_MAX:
+        return "--alternatives and --pin together may not ask for more than %d constraint sets" % MASKED_MAX
+    return None
+
+
+def check_pins_in_window(args, vcf_h):
+    """... and the one that needs the VCF (still before any GPU call): every POS of a --pin is a SNP of the window."""
+    for spec in args.pin or []:
+        for pos, _ in parse_pin(spec):
+            if pos not in vcf_h["snp_fwd"]:
+                return "--pin %s: position %d is not a SNP of the window" % (spec, pos)
+    return None
+
+
+def _reach(x, x0):
+    """(SNPs at which x differs from x0, the first and the last of them as SNP ranks; 0, 0, 0 where none does)."""
+    import numpy as np
+    d = np.flatnonzero(np.asarray(x)[1:] != np.asarray(x0)[1:]) + 1
+    return (len(d), int(d[0]), int(d[-1])) if len(d) else (0, 0, 0)
+
+
+def alternatives_text(head, res, alts, pinned, recovered, i0s, snp_rev):
+    """gretel.alternatives: "# N L cond_mode marginal_term S states M n" (`head` the first seven, M = 0 without --alternatives; n the
+    alternatives that follow), then, tab separated,
+      B  ll_chain, SNP string                                      the free best haplotype (set 0 of the call)
+      A  SNP rank p, genomic position, best allele, alternative allele, max-marginal gap, then the TAIL     one per alternative
+      P  k (the k-th --pin, from 1), pinned sites, then the TAIL                                             one per --pin
+    TAIL: ll_chain of the constrained best haplotype, ll_best - ll (0.0 where they are equal), the SNPs at which it differs from
+    the free best, the first and the last of them as SNP ranks (0 0 where none: how far the constraint reaches), the i_0 of the
+    nearest recovered haplotype and the SNPs at which they differ (-1 -1 where nothing was recovered), the SNP string.  An
+    infeasible set has "infeasible" and the first SNP rank without a candidate in place of the TAIL.
+    `res` is Hansel.viterbi_path_masked's dict over [all allowed] + alts["allow"] + the pin sets, `alts` alternatives_of's dict,
+    `pinned` the pinned sites per --pin, `recovered` the recovered haplotypes in out.fasta's order and `i0s` their i_0s."""
+    from .hansel import SYMBOLS
+    m = len(alts["p"])
+    lines = ["# %d\t%d\t%s\t%d\t%d\t%d\t%d\t%d\n" % (tuple(head) + (m,))]
+    x0, ll0 = res["paths"][0], float(res["ll_chain"][0])
+    near = nearest_recovered(res["paths"], recovered, i0s)
+
+    def tail(q):
+        if res["hole_at"][q]:
+            return "infeasible\t%d" % res["hole_at"][q]
+        ll = float(res["ll_chain"][q])
+        return "%.6f\t%.6f\t%d\t%d\t%d\t%d\t%d\t%s" % ((ll, 0.0 if ll == ll0 else ll0 - ll) + _reach(res["paths"][q], x0) + tuple(near[q]) +
+                                                      (Hansel.path_str(res["paths"][q][1:]),))
+
+    lines.append("B\t%.6f\t%s\n" % (ll0, Hansel.path_str(x0[1:])))
+    for q in range(m):
+        p = int(alts["p"][q])
+        lines.append("A\t%d\t%d\t%s\t%s\t%.6f\t%s\n" % (p, snp_rev[p - 1], SYMBOLS[int(alts["best"][q])], SYMBOLS[int(alts["alt"][q])],
+                                                      alts["gap"][q], tail(1 + q)))
+    for k, sites in enumerate(pinned):
+        lines.append("P\t%d\t%d\t%s\n" % (k + 1, sites, tail(1 + m + k)))
+    return "".join(lines)
+
+
+def write_alternatives(paths, unweighted, vcf_h, args, call=None):
+    """--alternatives / --pin: ONE constrained decoding of the copy taken before the spins -- set 0 all-allowed (the free best
+    haplotype), the alternatives_of sets of --alternatives M (from the max-marginals call it shares with --margins: `call`), one
+    set per --pin -- written to gretel.alternatives.  A window the decoder refuses: the library's message as a note and no file;
+    a hole of the window itself likewise; an infeasible --pin: a note and a line that says so."""
+    import numpy as np
+    from .hansel import allow_of, alternatives_of
+    n, order = unweighted.n, unweighted._cfg["cand_order"]
+    alts = dict(p=np.zeros(0, dtype=np.int32), best=np.zeros(0, dtype=np.uint8), alt=np.zeros(0, dtype=np.uint8), gap=np.zeros(0),
+                allow=np.zeros((0, n + 1), dtype=np.uint8))
+    if args.alternatives:
+        mres, info = call if call is not None else marginals_once(unweighted)
+        if mres is None:
+            sys.stderr.write("[NOTE] --alternatives: %s\n" % info)
+            return
+        if mres["hole_at"]:
+            sys.stderr.write("[NOTE] --alternatives: no candidate at SNP %d, no alternatives\n" % mres["hole_at"])
+            return
+        alts = alternatives_of(mres["mm"], mres["cm"], args.alternatives, order)
+    pins = [{vcf_h["snp_fwd"][pos] + 1: alleles for pos, alleles in parse_pin(spec)} for spec in args.pin or []]
+    allow = np.concatenate([allow_of(n).reshape(1, -1), alts["allow"]] + [allow_of(n, pins=pp).reshape(1, -1) for pp in pins])
+    try:
+        res = unweighted.viterbi_path_masked(allow)
+    except GretelHipError as e:
+        sys.stderr.write("[NOTE] --alternatives: %s\n" % e)
+        return
+    if res["hole_at"][0]:
+        sys.stderr.write("[NOTE] --alternatives: no candidate at SNP %d, no alternatives\n" % res["hole_at"][0])
+        return
+    m = len(alts["p"])
+    for k in range(len(pins)):
+        if res["hole_at"][1 + m + k]:
+            sys.stderr.write("[NOTE] --pin %d: no candidate at SNP %d under the constraints\n" % (k + 1, res["hole_at"][1 + m + k]))
+    s, _, states, _ = unweighted.viterbi_info()
+    keys = sorted(paths, key=lambda x: paths[x]["i_0"])
+    with open(args.out + "/gretel.alternatives", "w") as fh:
+        fh.write(alternatives_text(_score_head(unweighted, vcf_h) + (s, states, args.alternatives or 0), res, alts, [len(pp) for pp in pins],
+                                   _path_array(paths, keys, n), [paths[k]["i_0"] for k in keys], vcf_h["snp_rev"]))
 
 
 def kbest_text(head, res, per_rank, i0s):
@@ -502,7 +648,7 @@ def check_exact_options(args):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    bad = check_assign_options(args) or check_score_options(args) or check_beam_options(args) or check_exact_options(args) or check_kbest_options(args)
+    bad = check_assign_options(args) or check_score_options(args) or check_beam_options(args) or check_exact_options(args) or check_kbest_options(args) or check_masked_options(args)
     if bad:
         sys.stderr.write("[FAIL] %s\n" % bad)
         return 2
@@ -513,6 +659,10 @@ def main(argv=None):
         # (the BAM's blocks are read and inflated on the decoder's threads while the VCF is parsed here: include/gretel_io.h, gio_prefetch)
         util.prefetch_bam(args.bam, args.contig, args.start, args.end)
     vcf_h = util.process_vcf(args.vcf, args.contig, args.start, args.end)         # cmd.py:69
+    bad = check_pins_in_window(args, vcf_h)
+    if bad:
+        sys.stderr.write("[FAIL] %s\n" % bad)
+        return 2
     if args.dumpsnps:                                                             # cmd.py:70-74
         with open(args.dumpsnps, "w") as fh:
             for k in sorted(vcf_h["snp_fwd"].keys()):
@@ -529,7 +679,8 @@ def main(argv=None):
                                 stepper="all" if args.pepper else "samtools", keep_reads=args.assign_reads)     # cmd.py:78
     hansel.snapshot_original()                                                    # cmd.py:79 (what the copy is used for)
     # (the reference's copy of cmd.py:79, made only where something is scored against the matrix as the reads filled it)
-    unweighted = hansel.copy() if (args.score_paths or args.known or args.margins or args.kbest) else None
+    masked = bool(args.alternatives or args.pin)
+    unweighted = hansel.copy() if (args.score_paths or args.known or args.margins or args.kbest or masked) else None
     if args.dumpmatrix:
         hansel.save_hansel_dump(args.dumpmatrix)                                  # cmd.py:81-82
     if gap_report(hansel, vcf_h):
@@ -554,10 +705,13 @@ def main(argv=None):
         write_scores(paths, unweighted, vcf_h, args)
     if args.known:
         write_known(paths, unweighted, vcf_h, args)
+    marg = marginals_once(unweighted) if (args.margins or args.alternatives) else None      # (one call for the two of them)
     if args.margins:
-        write_margins(paths, unweighted, vcf_h, args)
+        write_margins(paths, unweighted, vcf_h, args, call=marg)
     if args.kbest:
         write_kbest(paths, unweighted, vcf_h, args)
+    if masked:
+        write_alternatives(paths, unweighted, vcf_h, args, call=marg)
     try:                       # the decoder's kept working buffers (include/gretel_io.h: GIO_KEEP_MB): a run has one decode
         from . import bamio
         if getattr(bamio, "_io", None) is not None:

@@ -194,6 +194,7 @@ struct gh_handle {
     int64_t beam_last[4];  // gh_beam_info: the last beam run on this handle
     dev_scratch vit;       // gh_viterbi_path / gh_viterbi_spin (viterbi.hpp): its chain table, N * states back-pointer bytes, the end row, the path
     int64_t vit_last[4];   // gh_viterbi_info: the last exact decoding on this handle
+    int64_t vitx_last[4];  // gh_viterbi_masked_info: the last constrained decoding on this handle (viterbi_masked.hpp)
     int cw_round_cap = env_int("GH_CW_ROUND_CAP", 0);   // =k at creation (tests): never more than k rounds per launch, so that chains stay open and the serial fallback runs
     gh_spin_plan last_plan;    // what the last gh_spin ran with (gh_debug_last_spin_plan; nothing else reads it)
     int spin_requeues;     // how often the last gh_spin rebuilt the table and queued the remaining paths again
@@ -3459,3 +3460,6 @@ static int check_symbol_rows(const uint8_t *paths, int n_paths, size_t n1, int c
 #include "viterbi_marg_panel.hpp"
 // ... and the k best haplotypes of every window: gh_panel_viterbi_kbest
 #include "viterbi_kbest_panel.hpp"
+// exact decoding under per-position allele masks, many constraint sets over one table: gh_viterbi_path_masked (the walk's body is
+// viterbi_panel.hpp's, hence behind it)
+#include "viterbi_masked.hpp"

@@ -155,6 +155,33 @@ inline vitk_bufs vitk_layout(void *base, int N, size_t table_doubles, int states
             c.take<uint8_t>(nk * n1), c.take<double>(nk), c.take<int32_t>(1), c.used};
 }
 
+// constrained decoding (viterbi_masked.hpp), in the exact decoder's block of the handle, `out` first for the same reason: the table
+// ONCE, and per constraint set a block of back-pointer bytes, the end row with its flags, a vit_out, a path row and the masks over
+// the five compact candidate indices.  A set's back-pointers are [N + 1][states] as the decoder's; `bps` = that rounded up to whole
+// words is the stride from set to set, so that every set's block starts on a four-byte boundary (k_vit_trace copies whole words,
+// and with an odd state count such as 3 or 9 a block would otherwise begin mid-word).  No slab scheme: the block grows with n_sets.
+struct vitx_bufs {
+    vit_out *out;
+    double *Gb;
+    uint8_t *bp;           // [n_sets] blocks of bps bytes
+    double *vend;          // [n_sets][states]
+    uint8_t *okend;        // [n_sets][states]
+    vit_out *outs;         // [n_sets]
+    uint8_t *paths;        // [n_sets][N + 1]
+    uint8_t *a5;           // [n_sets][N + 1] allowed bits over the compact indices
+    size_t bps;
+    size_t total;
+};
+
+inline vitx_bufs vitx_layout(void *base, int N, size_t table_doubles, int states, int n_sets)
+{
+    scratch_carver c{(char *)base};
+    const size_t n1 = (size_t)N + 1, ns = (size_t)states, m = (size_t)n_sets;
+    const size_t bps = (n1 * ns + 3) & ~(size_t)3;
+    return {c.take<vit_out>(1), c.take<double>(table_doubles), c.take<uint8_t>(m * bps), c.take<double>(m * ns), c.take<uint8_t>(m * ns),
+            c.take<vit_out>(m), c.take<uint8_t>(m * n1), c.take<uint8_t>(m * n1), bps, c.used};
+}
+
 // the exact decoder over a panel (viterbi_panel.hpp), a block of the batch: one descriptor per window (WD = vit_win, which holds
 // device types and so stands in viterbi_panel.hpp), the windows' vit_outs gathered for one copy to the host, and their path rows
 // gathered back to back (`path_bytes` = the sum of N_w + 1)

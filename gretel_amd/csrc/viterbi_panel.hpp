@@ -53,10 +53,22 @@ __device__ __forceinline__ void vit_union_body(const double *__restrict__ minfo,
 
 // dynamic LDS: [two score rows of `states` doubles] [STAGED: Le + 1 source blocks]
 // KEEP (viterbi_marg_panel.hpp): as k_vit_walk's -- `vend` is F[N][states], no back-pointers, no end row
-template <bool STAGED, bool KEEP = false>
+// MASKED (viterbi_masked.hpp): a5[0..N] holds the allowed bits of a constraint set over the compact indices; the candidate bits of
+// step p are ANDed with a5[p] before the hole test and before `hist` is shifted, so a predecessor's reachability (cm_old) is the
+// masked one without further code.  The bytes reach the step through a window of two chunks of VIT_MCH positions in LDS (512
+// static bytes, in the MASKED instantiations only): chunk c + 1 is stored in the middle of chunk c from a register of the first
+// VIT_MCH threads, into which it set out from global memory a whole chunk earlier, and the byte of step p + 1 is read from the
+// window in step p.  So no step waits for a global load of its own: the one wait for global memory the masks cost falls once in
+// VIT_MCH steps, on a load that has had VIT_MCH steps to arrive.  (A plain a5[p + 1] in step p does NOT do that: the byte is the
+// same in every thread, the compiler moves it into a scalar register right behind the load and drains vmcnt there -- the table
+// block's piece and the back-pointer stores with it, 0.2-0.3 us in every step; profiles/r19_masked.txt.)  MASKED = false (every
+// other shell) never touches a5 or the window, and those instantiations are the kernels they were.
+#define VIT_MCH 256
+template <bool STAGED, bool KEEP = false, bool MASKED = false>
 __device__ __forceinline__ void
 vit_walk_body(const double *__restrict__ Gb, int N, int L, int S, int states, int marginal_term, uint32_t U,
-              uint8_t *__restrict__ bp, double *__restrict__ vend, uint8_t *__restrict__ okend, vit_out *__restrict__ out)
+              uint8_t *__restrict__ bp, double *__restrict__ vend, uint8_t *__restrict__ okend, vit_out *__restrict__ out,
+              const uint8_t *__restrict__ a5 = nullptr)
 {
     extern __shared__ __attribute__((aligned(16))) char vit_smem[];
     const int tid = threadIdx.x;
@@ -116,7 +128,15 @@ vit_walk_body(const double *__restrict__ Gb, int N, int L, int S, int states, in
         if (tid < su) tab2[tid] = Gb2[tid];                   // source 0 straight in; source 1 sets out
         if (1 < N && tid < su) reg = Gb2[(size_t)su + tid];
     }
+    __shared__ uint8_t vit_mk[MASKED ? 2 * VIT_MCH : 4];       // MASKED: the window; position q lies at q mod 2 VIT_MCH
+    uint32_t allow = 31u, allow_next = 31u;                   // ... the allowed bits of step p, those of step p + 1
+    uint8_t mreg = 31;                                        // ... and a byte of the chunk that is on its way
+    if (MASKED) {
+        if (tid < VIT_MCH && tid <= N) vit_mk[tid] = a5[tid];                   // chunk 0 straight in; chunk 1 sets out
+        if (tid < VIT_MCH && VIT_MCH + tid <= N) mreg = a5[VIT_MCH + tid];
+    }
     __syncthreads();
+    if (MASKED) allow = vit_mk[1];
 
     int cur = 0, hole = 0;
     int ts = 0;                                               // LDS slot of source p - 1
@@ -127,8 +147,18 @@ vit_walk_body(const double *__restrict__ Gb, int N, int L, int S, int states, in
             if (p < N && tid < su) tab2[(size_t)ws * su + tid] = reg;
             if (p + 1 < N && tid < su) reg = Gb2[(size_t)(p + 1) * su + tid];
         }
+        if (MASKED) {
+            if ((p & (VIT_MCH - 1)) == VIT_MCH / 2) {
+                // chunk c + 1 (first read in step nx - 1) replaces chunk c - 1, last read in step nx - VIT_MCH - 2; chunk c + 2 sets out
+                const int nx = (p / VIT_MCH + 1) * VIT_MCH;
+                if (tid < VIT_MCH) vit_mk[(nx + tid) & (2 * VIT_MCH - 1)] = mreg;
+                if (tid < VIT_MCH && nx + VIT_MCH + tid <= N) mreg = a5[nx + VIT_MCH + tid];
+            }
+            if (p < N) allow_next = vit_mk[(p + 1) & (2 * VIT_MCH - 1)];
+        }
         const double *blk = STAGED ? tab + (size_t)ts * sd : Gb + (size_t)(p - 1) * sd;
-        const uint32_t cm5 = (uint32_t)__double_as_longlong(blk[30 * L + 5]) & 31u;
+        uint32_t cm5 = (uint32_t)__double_as_longlong(blk[30 * L + 5]) & 31u;
+        if (MASKED) cm5 &= allow;
         if (cm5 == 0) { hole = p; break; }                    // (the same word in every thread: all leave together)
         const uint32_t cm_old = one ? 1u << slot_of[0] : (uint32_t)(hist >> (5 * (L - 1))) & 31u;      // what position p - Le offers
         hist = ((hist << 5) | cm5) & hmask;
@@ -175,6 +205,7 @@ vit_walk_body(const double *__restrict__ Gb, int N, int L, int S, int states, in
         }
         cur ^= 1;
         ts = ts + 1 == R ? 0 : ts + 1;
+        if (MASKED) allow = allow_next;
         beam_barrier();
     }
     if (tid == 0) out->hole_at = hole;

@@ -154,6 +154,65 @@ def kbest_of(res, recovered=None):
     return out
 
 
+def _allele_bits(who, symbols):
+    """The bits over the seven symbols of `symbols`: characters of "ACGT-" or their indices (0, 1, 2, 3, 5), one or several."""
+    if isinstance(symbols, (int, np.integer)):
+        symbols = [symbols]
+    bits = 0
+    for s in symbols:
+        if isinstance(s, str):
+            i = SYMBOLS.index(s) if s in SYMBOLS else -1
+        else:
+            i = int(s)
+        if i not in (0, 1, 2, 3, 5):
+            raise ValueError("%s: %r is no allele of ACGT-" % (who, s))
+        bits |= 1 << i
+    return bits
+
+
+def allow_of(n, pins=None, bans=None):
+    """One constraint set of Hansel.viterbi_path_masked for a window of n SNPs: uint8[n+1], all 0x7f (everything allowed) except
+    where given.  Host only.  pins {p: symbols}: only these are allowed at SNP p; bans {p: symbols}: these are not (a ban on a
+    pinned position takes from the pinned ones).  Symbols are characters of "ACGT-" or symbol indices, one or several.
+    ValueError for a p outside 1..n or a symbol outside the five."""
+    allow = np.full(int(n) + 1, 0x7F, dtype=np.uint8)
+    for what, table in (("pins", pins), ("bans", bans)):
+        for p, symbols in (table or {}).items():
+            if not 1 <= int(p) <= n:
+                raise ValueError("allow_of: %s at SNP %r, outside 1..%d" % (what, p, n))
+            bits = _allele_bits("allow_of", symbols)
+            allow[int(p)] = bits if what == "pins" else int(allow[int(p)]) & ~bits & 0x7F
+    return allow
+
+
+def alternatives_of(mm, cm, m, cand_order="ACGT-"):
+    """The constraint sets `--alternatives m` decodes, and what they pin.  Host only.  mm, cm: Hansel.viterbi_marginals' table.
+    Of the SNPs that offer at least two candidates the m of smallest margins_of gap (ascending gap, then ascending p); per SNP the
+    runner-up is the offered candidate other than best[p] of largest mm[p][.], the first of cand_order among equals, and its set
+    is all-allowed with allow[p] = 1 << runner-up: the best haplotype that carries the runner-up there.  Returns dict(p int32[m'],
+    best uint8[m'], alt uint8[m'], gap float64[m'], allow uint8[m'][N+1]) with m' <= m."""
+    mm = np.asarray(mm, dtype=np.float64)
+    cm = np.asarray(cm, dtype=np.uint8)
+    n = len(cm) - 1
+    marg = margins_of(mm, cm, [], cand_order)
+    order = [SYMBOLS.index(c) for c in cand_order]
+    offered = {p: [s for s in order if (int(cm[p]) >> s) & 1] for p in range(1, n + 1)}
+    ps = sorted((p for p in offered if len(offered[p]) >= 2), key=lambda p: (marg["gap"][p], p))[:max(0, int(m))]
+    alt = []
+    for p in ps:
+        others = [s for s in offered[p] if s != marg["best"][p]]
+        r = others[0]
+        for s in others[1:]:
+            if mm[p, s] > mm[p, r]:
+                r = s
+        alt.append(r)
+    allow = np.full((len(ps), n + 1), 0x7F, dtype=np.uint8)
+    for q, (p, r) in enumerate(zip(ps, alt)):
+        allow[q, p] = 1 << r
+    return dict(p=np.array(ps, dtype=np.int32), best=marg["best"][ps].astype(np.uint8) if ps else np.zeros(0, dtype=np.uint8),
+                alt=np.array(alt, dtype=np.uint8), gap=marg["gap"][ps] if ps else np.zeros(0), allow=allow)
+
+
 class Hansel:
     def __init__(self, n_snps, band=None, storage="f32", cond_mode="A", marginal_term=False, device=-1,
                  cand_order="ACGT-", offer_zero=False):
@@ -541,6 +600,32 @@ class Hansel:
         n, hole = C.c_int(), C.c_int()
         check(self._lib.gh_viterbi_kbest(self._h, k, _p(paths), _p(ll), C.byref(n), C.byref(hole)))
         return dict(n=n.value, hole_at=hole.value, paths=paths[:n.value], ll_chain=ll[:n.value])
+
+    def viterbi_path_masked(self, allow):
+        """Exact decoding under per-position allele masks, one constraint set per row of `allow` (gh_viterbi_path_masked; the
+        definition: INTEGRATION.md "Constrained decoding").  allow: uint8[n_sets][N+1] or one uint8[N+1], bit s of allow[.][p] set =
+        symbol s (ACGTN-_) is allowed at SNP p (allow_of() builds a row from pins and bans); at most 256 sets a call, decoded side
+        by side over one table.  Returns dict(paths uint8[n_sets][N+1], ll_chain float64[n_sets], hole_at int32[n_sets]): per set
+        the best full path that respects it and its chain likelihood, exactly.  Where a set leaves some SNP p without a candidate,
+        hole_at is p, ll_chain NaN (-inf is a legitimate score) and the row all 6.  Served where viterbi_path() is.  The tensor is
+        not touched."""
+        self._ensure()
+        allow = np.ascontiguousarray(allow, dtype=np.uint8)
+        if allow.ndim == 1:
+            allow = allow.reshape(1, -1)
+        if allow.ndim != 2 or allow.shape[1] != self.n + 1:
+            raise ValueError("viterbi_path_masked: allow must be [n_sets][N+1] with N+1 = %d (got %s)" % (self.n + 1, allow.shape))
+        m = len(allow)
+        paths = np.full((m, self.n + 1), 6, dtype=np.uint8)
+        ll = np.full(m, np.nan)
+        hole = np.zeros(m, dtype=np.int32)
+        check(self._lib.gh_viterbi_path_masked(self._h, _p(allow), m, _p(paths), _p(ll), _p(hole)))
+        return dict(paths=paths, ll_chain=ll, hole_at=hole)
+
+    def viterbi_masked_info(self):
+        """The last viterbi_path_masked() on this handle (gh_viterbi_masked_info): (sets, sets that met a hole, walk launches,
+        bytes of the decoder's device scratch)."""
+        return self._info4(self._lib.gh_viterbi_masked_info)
 
     def viterbi_kbest_max(self):
         """The largest k viterbi_kbest() takes on the tensor as it stands: min(32, 4096 // states) from viterbi_states(), and 0

@@ -424,6 +424,46 @@ int gh_viterbi_marginals(gh_t *h, double *mm /*[N+1][7]*/, uint8_t *cm /*[N+1]*/
 #define GH_KBEST_MAX 32
 int gh_viterbi_kbest(gh_t *h, int k, uint8_t *paths_out /*[k][N+1]*/, double *ll_chain /*[k]*/, int *n_out, int *hole_at);
 
+/* Constrained exact decoding of the chain likelihood (no reference counterpart; INTEGRATION.md "Constrained decoding").  The
+ * max-marginals say what the best full path through (p, c) scores; this returns that path -- and the best completion of any
+ * partly known haplotype: exact decoding under per-position allele masks (pins and bans), many constraint sets over one window in
+ * one call.  Notation as in "Exact decoding" above.
+ *   A constraint set is allow[0..N], one byte per position: bit s set = symbol s (index order ACGTN-_) is allowed at p.  allow[0]
+ *   and the bits of N and '_' are ignored; bit 7 set is an error.  The masked candidate set is cm'(p) = cm(p) & allow[p].  A full
+ *   path has x[p] in cm'(p) for p = 1..N; score(x) is unchanged, gh_score_paths' ll_chain.
+ *   Result per set: the maximum of score(x) over the full paths of the masked window, attained exactly; the path is the one kept
+ *   by gh_viterbi_path's procedure run over cm': the same competition rule for p > Le, the same end rule.
+ *   Hole: at the first p with empty cm'(p), hole_at[set] = p, and neither that set's path row nor its score is written; the other
+ *   sets run on.  A mask can make a hole where the window has none: that is a value ("infeasible at p"), not an error.
+ *   Otherwise hole_at[set] = 0.
+ *   State space: U, S and S^Le are those of the UNMASKED window as it stands, for every set: the call serves exactly the windows
+ *   gh_viterbi_path serves and refuses the others with the same message.  A mask only removes reachable states; the tie rules are
+ *   stated in q(), not in digits, so this choice is invisible in the results.
+ *   Hence:
+ *     allow all 0x7f gives gh_viterbi_path's path and score, bit for bit;
+ *     ll_chain[set] == gh_score_paths(paths[set]).ll_chain with n_on == N, and every x[p] is allowed;
+ *     one-hot masks of a full path x at all positions return x and its gh_score_paths score;
+ *     one-hot masks of the unmasked best path x* at any subset of positions return x* and its score (fl(a + w) is monotone in a:
+ *     a competitor that x*'s prefix strictly beat, or tied with priority, in the full problem can only score lower in the
+ *     restricted one);
+ *     a pin (N, c) gives ll == mm[N][c] of gh_viterbi_marginals exactly (B_N = +0.0); for any p the maximum over c in cm(p) of the
+ *     pinned scores equals gh_viterbi_path's ll_chain exactly; for p < N a pinned score and mm[p][c] differ only by the
+ *     summation order, within the bound stated under "Max-marginals".
+ * GH_ERR_ARG for a null argument, n_sets outside 0..GH_MASKED_MAX_SETS, an allow byte with bit 7 set, offer_zero, or more than
+ * GH_VITERBI_MAX_STATES states (gh_viterbi_path's message); GH_ERR_STATE before any fill.  n_sets == 0 returns GH_OK and writes
+ * nothing -- on a window the call serves: the refusals above come first, the cap included.  A window that offers nothing anywhere gives hole_at = 1 for every set.  GH_ERR_NOMEM names the size of the scratch: the
+ * exact decoder's block of the handle (kept until gh_destroy), here the table ONCE, and per set (N + 1) * S^Le back-pointer
+ * bytes (each set's block on a four-byte boundary), the end row, a path row and the compacted masks.  There is no slab or budget
+ * scheme: 256 sets at 10k SNPs and 4096 states are 10.5 GB.
+ * It only reads the tensor: the band, L, the fill statistics, the snapshot, the handle's conditional tables and the results of a
+ * following gh_spin stay as they are, bit for bit.  gh_viterbi_info afterwards describes this call: S, Le, states, bytes.
+ * gh_viterbi_masked_info, the last such call on the handle: out[0] = sets, out[1] = sets that met a hole, out[2] = walk launches,
+ * out[3] = scratch bytes (all 0 before the first). */
+#define GH_MASKED_MAX_SETS 256
+int gh_viterbi_path_masked(gh_t *h, const uint8_t *allow /*[n_sets][N+1]*/, int n_sets,
+                           uint8_t *paths_out /*[n_sets][N+1]*/, double *ll_chain /*[n_sets]*/, int *hole_at /*[n_sets]*/);
+int gh_viterbi_masked_info(const gh_t *h, int64_t out[4]);
+
 /* gh_viterbi_spin over every window of a batch or panel, the decoders of a round side by side: a window's exact decoder is ONE
  * workgroup, so one launch with a workgroup per window decodes all of them in about the time of the slowest.
  * Window w's paths ([max_paths][N_w + 1] at paths_out + paths_off[w], as gh_panel_spin; for a batch paths_off[w] =
