@@ -18,6 +18,7 @@ GH_STORAGE = {"f32": 0, "f64": 1}
 GH_COND = {"A": 0, "B": 1, "C": 2, "D": 3, "E": 4}
 GH_BEAM_MAX = 32
 GH_VITERBI_MAX_STATES = 4096
+GH_VITERBI_GRID_MAX_STATES = 1 << 24
 GH_KBEST_MAX = 32
 GH_MASKED_MAX_SETS = 256
 GH_K = {"fill": 0, "marg": 1, "lt": 2, "walk": 3, "reweight": 4, "seg": 5, "rwseg": 6}
@@ -164,6 +165,9 @@ def load():
         "gh_viterbi_spin": [vp, i32, dbl, vp, vp, vp, P(i32), P(i32)],
         "gh_viterbi_info": [vp, vp],
         "gh_viterbi_states": [vp, vp],
+        "gh_viterbi_path_grid": [vp, vp, P(dbl), P(i32)],
+        "gh_viterbi_spin_grid": [vp, i32, dbl, vp, vp, vp, P(i32), P(i32)],
+        "gh_viterbi_grid_info": [vp, vp],
         "gh_viterbi_marginals": [vp, vp, vp, P(i32)],
         "gh_viterbi_kbest": [vp, i32, vp, vp, P(i32), P(i32)],
         "gh_viterbi_path_masked": [vp, vp, i32, vp, vp, vp],

@@ -18,6 +18,10 @@ the chain likelihood; --beam 1 writes what a run without the flag writes.
 and, with --exact (INTEGRATION.md "Exact decoding"), the same files from paths that are each the global maximum of the chain
 likelihood on the matrix at that moment; a window with more than 4096 states ends the run with the library's message, status 1.
 
+and, with --exact-grid (INTEGRATION.md "Exact decoding on the grid"), the same through the grid decoder, which serves up to 2^24
+states -- the fill's own L = 10 on a window of four or five candidate symbols -- at a kernel launch per SNP; a note on stderr says
+what it is about to allocate.
+
 and, with --margins (INTEGRATION.md "Max-marginals"), against the matrix as it was before any reweighting:
     <out>/gretel.margins  "# N L cond_mode marginal_term S states", one "H" line per recovered haplotype (i_0, n_best, max_regret and
                           the genomic position of argmax_regret) and one "S" line per SNP (genomic position, best allele, gap, the
@@ -59,6 +63,7 @@ from .hansel import Hansel
 MIN_REMOVE = 0.01          # cmd.py:157
 BEAM_MAX = 32              # include/gretel_hip.h: GH_BEAM_MAX
 EXACT_MAX_STATES = 4096    # include/gretel_hip.h: GH_VITERBI_MAX_STATES
+GRID_MAX_STATES = 1 << 24  # include/gretel_hip.h: GH_VITERBI_GRID_MAX_STATES
 KBEST_MAX = 32             # include/gretel_hip.h: GH_KBEST_MAX
 MASKED_MAX = 255           # include/gretel_hip.h: GH_MASKED_MAX_SETS less the free best path, which is set 0 of the call
 MARGINS_HELP = ("compute the max-marginals of the chain likelihood on the unreweighted matrix (per SNP and allele the best likelihood "
@@ -98,6 +103,9 @@ def build_parser():
     p.add_argument("--exact", action="store_true", help="recover every path as the global maximum of the chain likelihood (exact "
                    "decoding over S^min(L, N) states, at most %d: L <= 6 without deletion columns, L <= 5 with them) instead of "
                    "the greedy walk" % EXACT_MAX_STATES)
+    p.add_argument("--exact-grid", action="store_true", help="--exact through the grid decoder: the same paths, for up to %d states "
+                   "(L <= 12 without deletion columns, L <= 10 with them) at a kernel launch per SNP and a byte of device memory per "
+                   "SNP and state; with --exact it is what runs" % GRID_MAX_STATES)
     p.add_argument("--margins", action="store_true", help=MARGINS_HELP)
     p.add_argument("--kbest", type=int, default=None, metavar="K", help=KBEST_HELP)
     p.add_argument("--alternatives", type=int, default=None, metavar="M", help="for the M SNPs whose call is least certain (smallest "
@@ -213,12 +221,18 @@ def _add_path(paths, i, key, hansel_path, hp_current, hp_original, magnitude):
     rec["hp_original"].append(hp_original)
 
 
-def recover(hansel, n_snps, max_paths, log=None, beam=0, exact=False):
+def recover(hansel, n_snps, max_paths, log=None, beam=0, exact=False, grid=False):
     """cmd.py:148-179 on the device; returns the PATHS table in order of discovery.  The spins have already
     happened when the notes are written, but the notes are the reference's, in the reference's order.
     beam >= 1 (--beam): every path is the best of a beam of that many hypotheses (Hansel.beam_spin).
-    exact (--exact): every path is the global maximum of the chain likelihood (Hansel.viterbi_spin)."""
-    if exact:
+    exact (--exact): every path is the global maximum of the chain likelihood (Hansel.viterbi_spin).
+    grid (--exact-grid): the same through the grid decoder (Hansel.viterbi_spin_grid), behind a note of what it allocates."""
+    if grid:
+        s, le, states = hansel.viterbi_states()
+        (log or sys.stderr).write("[NOTE] --exact-grid: S = %d candidate symbols, Le = %d: %d states, %d bytes of device scratch\n"
+                                  % (s, le, states, hansel.viterbi_grid_bytes()))
+        res = hansel.viterbi_spin_grid(max_paths, MIN_REMOVE)
+    elif exact:
         res = hansel.viterbi_spin(max_paths, MIN_REMOVE)
     else:
         res = hansel.beam_spin(beam, max_paths, MIN_REMOVE) if beam else hansel.spin(max_paths, MIN_REMOVE)
@@ -638,10 +652,11 @@ def check_beam_options(args):
 
 
 def check_exact_options(args):
-    """The refusals of --exact (before any BAM read or GPU call): a message, or None."""
-    if args.exact and args.beam:
+    """The refusals of --exact and --exact-grid (before any BAM read or GPU call): a message, or None."""
+    exact = args.exact or getattr(args, "exact_grid", False)     # (gretel_amd.panel's parser has no --exact-grid)
+    if exact and args.beam:
         return "--exact cannot be combined with --beam: a path is either the global maximum or the best of a beam"
-    if args.exact and debug_hpos_of(args):
+    if exact and debug_hpos_of(args):
         return "--exact cannot be combined with --debughpos, which prints the branch weights of the greedy walk"
     return None
 
@@ -692,9 +707,9 @@ def main(argv=None):
         paths = recover_with_debug(hansel, vcf_h["N"], args.paths, debug_hpos)
     else:
         try:
-            paths = recover(hansel, vcf_h["N"], args.paths, beam=args.beam, exact=args.exact)
+            paths = recover(hansel, vcf_h["N"], args.paths, beam=args.beam, exact=args.exact, grid=args.exact_grid)
         except GretelHipError as e:
-            if not args.exact:
+            if not (args.exact or args.exact_grid):
                 raise
             sys.stderr.write("[FAIL] %s\n" % e)                                   # (more states than the decoder holds: no fallback)
             return 1

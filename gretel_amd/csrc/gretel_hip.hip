@@ -32,6 +32,7 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "gretel_hip.h"
@@ -195,6 +196,7 @@ struct gh_handle {
     dev_scratch vit;       // gh_viterbi_path / gh_viterbi_spin (viterbi.hpp): its chain table, N * states back-pointer bytes, the end row, the path
     int64_t vit_last[4];   // gh_viterbi_info: the last exact decoding on this handle
     int64_t vitx_last[4];  // gh_viterbi_masked_info: the last constrained decoding on this handle (viterbi_masked.hpp)
+    int64_t vitg_last[4];  // gh_viterbi_grid_info: the last decoding on the grid on this handle (viterbi_grid.hpp)
     int cw_round_cap = env_int("GH_CW_ROUND_CAP", 0);   // =k at creation (tests): never more than k rounds per launch, so that chains stay open and the serial fallback runs
     gh_spin_plan last_plan;    // what the last gh_spin ran with (gh_debug_last_spin_plan; nothing else reads it)
     int spin_requeues;     // how often the last gh_spin rebuilt the table and queued the remaining paths again
@@ -3463,3 +3465,6 @@ static int check_symbol_rows(const uint8_t *paths, int n_paths, size_t n1, int c
 // exact decoding under per-position allele masks, many constraint sets over one table: gh_viterbi_path_masked (the walk's body is
 // viterbi_panel.hpp's, hence behind it)
 #include "viterbi_masked.hpp"
+// exact decoding beyond the states two LDS rows hold: the score rows in global memory, one launch per position (gh_viterbi_path_grid,
+// gh_viterbi_spin_grid, gh_viterbi_grid_info)
+#include "viterbi_grid.hpp"

@@ -182,6 +182,37 @@ inline vitx_bufs vitx_layout(void *base, int N, size_t table_doubles, int states
             c.take<vit_out>(m), c.take<uint8_t>(m * n1), c.take<uint8_t>(m * n1), bps, c.used};
 }
 
+// the grid decoder (viterbi_grid.hpp), in the exact decoder's block of the handle.  `out` is the first part as above, and the
+// candidate bytes stand right behind it under both sizings: the call reserves the block with `states` = 0 while only k_vit_cands'
+// bytes are wanted (they say how many states there are), then in full.  What grows: a back-pointer byte per position and state
+// (at 2^24 states and 128 SNPs they alone pass 2^31 bytes, so every product with `states` or N is formed in size_t) and the two
+// score rows.  The end rule's first level leaves one (score, state) per GH_VITG_END_CHUNK states.
+#define GH_VITG_END_CHUNK 4096
+
+struct vitg_bufs {
+    vit_out *out;
+    uint8_t *cm5, *cm;     // [N + 1] each: candidate bits over the compact indices (what the host reads) and over the seven symbols
+    double *Gb;
+    uint8_t *bp;           // [N + 1][states]
+    double *rows;          // [2][states]
+    double *pv;            // [parts] the end rule's partial maxima ...
+    int32_t *pj;           // [parts] ... and their states, -1 = no reachable state in the chunk
+    uint8_t *path;         // [N + 1]
+    size_t parts;
+    size_t total;
+};
+
+inline vitg_bufs vitg_layout(void *base, int N, size_t table_doubles, size_t states)
+{
+    scratch_carver c{(char *)base};
+    const size_t n1 = (size_t)N + 1, parts = (states + GH_VITG_END_CHUNK - 1) / GH_VITG_END_CHUNK;
+    vit_out *out = c.take<vit_out>(1);
+    uint8_t *cm5 = c.take<uint8_t>(n1), *cm = c.take<uint8_t>(n1);
+    if (!states) return {out, cm5, cm, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, c.used};
+    return {out, cm5, cm, c.take<double>(table_doubles), c.take<uint8_t>(n1 * states), c.take<double>(2 * states), c.take<double>(parts),
+            c.take<int32_t>(parts), c.take<uint8_t>(n1), parts, c.used};
+}
+
 // the exact decoder over a panel (viterbi_panel.hpp), a block of the batch: one descriptor per window (WD = vit_win, which holds
 // device types and so stands in viterbi_panel.hpp), the windows' vit_outs gathered for one copy to the host, and their path rows
 // gathered back to back (`path_bytes` = the sum of N_w + 1)

@@ -170,6 +170,24 @@ def _allele_bits(who, symbols):
     return bits
 
 
+def grid_scratch_bytes(n, le, states):
+    """vitg_layout's total (gretel_amd/csrc/scratch_layout.hpp) for a window of n SNPs, Le lags and `states` states: what a grid
+    decoding reserves.  Host only.  Every part starts on a 256-byte boundary: the decoder's result words, two rows of n + 1
+    candidate bytes, the table (n sources of 30 Le + 6 doubles), a back-pointer byte per position and state, two score rows, a
+    (score, state) per 4096 states for the end rule, the path row.  0 beyond the grid decoder's cap; no states (nothing offered
+    anywhere) leaves the first three parts."""
+    def up(x):
+        return (x + 255) & ~255
+    if states > _lib.GH_VITERBI_GRID_MAX_STATES:
+        return 0
+    n1 = int(n) + 1
+    head = up(24) + 2 * up(n1)
+    if states < 1:
+        return head
+    parts = (states + 4095) // 4096
+    return head + up(n * (30 * le + 6) * 8) + up(n1 * states) + up(16 * states) + up(8 * parts) + up(4 * parts) + up(n1)
+
+
 def allow_of(n, pins=None, bans=None):
     """One constraint set of Hansel.viterbi_path_masked for a window of n SNPs: uint8[n+1], all 0x7f (everything allowed) except
     where given.  Host only.  pins {p: symbols}: only these are allowed at SNP p; bans {p: symbols}: these are not (a ban on a
@@ -553,7 +571,7 @@ class Hansel:
         """The full path of largest chain likelihood on the tensor as it is now, exactly (gh_viterbi_path; the definition and
         the tie rule: INTEGRATION.md "Exact decoding").  Returns dict(path uint8[N+1], ll_chain, hole_at); at a hole path and
         ll_chain are None.  Served where S^min(L, N) <= 4096 states (S = the candidate symbols the window offers); beyond that
-        GretelHipError, and the beam is the tool.  The tensor is not touched."""
+        GretelHipError, and viterbi_path_grid() (up to 2^24 states) or the beam is the tool.  The tensor is not touched."""
         self._ensure()
         path = np.zeros(self.n + 1, dtype=np.uint8)
         ll, hole = C.c_double(), C.c_int()
@@ -642,6 +660,34 @@ class Hansel:
         out = np.zeros(3, dtype=np.int64)
         check(self._lib.gh_viterbi_states(self._h, _p(out)))
         return tuple(int(v) for v in out)
+
+    def viterbi_path_grid(self):
+        """viterbi_path() through the grid decoder (gh_viterbi_path_grid; INTEGRATION.md "Exact decoding on the grid"): the same
+        definition and the same dict, bit for bit where both serve a window, for up to 2^24 states -- the score rows lie in device
+        memory and every SNP is a kernel launch.  Always the grid kernels, whatever the state count; viterbi_grid_bytes() says
+        beforehand what it reserves.  The tensor is not touched."""
+        self._ensure()
+        path = np.zeros(self.n + 1, dtype=np.uint8)
+        ll, hole = C.c_double(), C.c_int()
+        check(self._lib.gh_viterbi_path_grid(self._h, _p(path), C.byref(ll), C.byref(hole)))
+        if hole.value:
+            return dict(path=None, ll_chain=None, hole_at=hole.value)
+        return dict(path=path, ll_chain=ll.value, hole_at=0)
+
+    def viterbi_spin_grid(self, max_paths=100, min_remove=0.01):
+        """viterbi_spin() with the grid decoding per path (gh_viterbi_spin_grid): the same dict."""
+        return self._decode_spin(self._lib.gh_viterbi_spin_grid, max_paths=max_paths, min_remove=min_remove)
+
+    def viterbi_grid_info(self):
+        """The last grid decoding on this handle (gh_viterbi_grid_info): viterbi_info()'s tuple, (S, Le, states, bytes of the
+        device scratch it reserved); all 0 before the first."""
+        return self._info4(self._lib.gh_viterbi_grid_info)
+
+    def viterbi_grid_bytes(self):
+        """The device scratch a grid decoding of the tensor as it stands reserves where it meets no hole, and 0 where the window
+        is beyond the grid decoder's cap.  Host arithmetic over viterbi_states(): vitg_layout of gretel_amd/csrc/scratch_layout.hpp."""
+        _, le, states = self.viterbi_states()
+        return grid_scratch_bytes(self.n, le, states)
 
     def clear(self):
         self._staged = []

@@ -359,6 +359,33 @@ int gh_viterbi_info(const gh_t *h, int64_t out[4]);
  * a caller can tell beforehand which windows the decoder serves.  Only the handle's marginal tables are brought up to date. */
 int gh_viterbi_states(gh_t *h, int64_t out[3]);
 
+/* Exact decoding on the grid (INTEGRATION.md "Exact decoding on the grid"): the decoder above keeps its two score rows in the
+ * on-chip memory of one workgroup, hence its cap; the fill's own L = ceil(mean SNPs per read) is often beyond it (L = 10 on a
+ * window of 60 SNPs: 4^10 or 5^10 states).  The grid decoder is a second exact decoder under the SAME definition -- score, tie
+ * rule during the walk, tie rule at the end, hole rule, the refusal of offer_zero, every addition in the same order -- with the
+ * score rows in device memory and one kernel launch per SNP, each a grid over the states.  No workgroup waits for another; the
+ * launch boundary is the only synchronisation.  It serves S^Le <= GH_VITERBI_GRID_MAX_STATES = 2^24 = 4^12 (5^10 lies below it;
+ * with S >= 2 that bounds Le at 24).
+ *   Where both serve a window, path, ll_chain and hole_at of gh_viterbi_path_grid equal gh_viterbi_path's bit for bit, under every
+ *   spec and candidate order, also where every path scores +inf (conditionals C and D) or -inf.  The grid calls always run the
+ *   grid kernels, also on a window of 64 states (where the launch per SNP costs more than the other decoder's whole step).
+ *   gh_viterbi_spin_grid is gh_viterbi_spin with the grid decoding per path.
+ * The refusals are gh_viterbi_path's with this cap in place of that one: GH_ERR_ARG for a null argument (ll_chain of the spin may
+ * be NULL), max_paths < 0, offer_zero, or S^Le > GH_VITERBI_GRID_MAX_STATES (the message names S, Le, the count and the cap, and
+ * points to the beam; nothing is allocated for such a window).  GH_ERR_STATE before any fill.  GH_ERR_NOMEM names the bytes.  The
+ * scratch is the exact decoder's block of the handle, kept until gh_destroy: the table, N * (30 Le + 6) * 8 bytes, one
+ * back-pointer byte per position and state, (N + 1) * S^Le bytes, and two score rows, 16 * S^Le bytes -- 0.08 GB at 60 SNPs and
+ * 4^10 states, 0.75 GB at 5^10, 168 GB at 10k SNPs and the cap: ask gh_viterbi_states first.  A hole is found on the host, from
+ * the candidate bits, before any of that is reserved.
+ * The calls only read the tensor (the spin reweights it as gh_viterbi_spin does); gh_viterbi_info is not touched.
+ * gh_viterbi_grid_info, the last grid call on the handle: out[0] = S, out[1] = Le, out[2] = states = S^Le, out[3] = bytes of
+ * the scratch it reserved (all 0 before the first). */
+#define GH_VITERBI_GRID_MAX_STATES 16777216
+int gh_viterbi_path_grid(gh_t *h, uint8_t *path_out /*[N+1]*/, double *ll_chain, int *hole_at);
+int gh_viterbi_spin_grid(gh_t *h, int max_paths, double min_remove, uint8_t *paths_out /*[max_paths][N+1]*/,
+                         gh_path_rec *recs, double *ll_chain /*[max_paths], may be NULL*/, int *n_out, int *hole_at);
+int gh_viterbi_grid_info(const gh_t *h, int64_t out[4]);
+
 /* Max-marginals of the chain likelihood (no reference counterpart; INTEGRATION.md "Max-marginals").  gh_score_paths' margin says
  * what one greedy step would have lost with the history held fixed; this says, for every SNP p and every candidate c, the best
  * chain likelihood of ANY full path that takes c at p -- everything else free to re-optimise around the choice.  Notation as in
