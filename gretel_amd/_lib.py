@@ -169,6 +169,7 @@ def load():
         "gh_viterbi_spin_grid": [vp, i32, dbl, vp, vp, vp, P(i32), P(i32)],
         "gh_viterbi_grid_info": [vp, vp],
         "gh_viterbi_marginals": [vp, vp, vp, P(i32)],
+        "gh_viterbi_marginals_grid": [vp, vp, vp, P(i32)],
         "gh_viterbi_kbest": [vp, i32, vp, vp, P(i32), P(i32)],
         "gh_viterbi_path_masked": [vp, vp, i32, vp, vp, vp],
         "gh_viterbi_masked_info": [vp, vp],

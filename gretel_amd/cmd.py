@@ -28,6 +28,9 @@ and, with --margins (INTEGRATION.md "Max-marginals"), against the matrix as it w
                           regret of A C G T - with "." where an allele is not offered); nothing where the window has more than
                           4096 states (the library's message on stderr, the run goes on)
 
+and, with --margins-grid (INTEGRATION.md "Max-marginals on the grid"), the same file through the grid call, which serves up to 2^24
+states: byte for byte what --margins writes where both serve the window; a note on stderr says what it is about to allocate.
+
 and, with --kbest K (INTEGRATION.md "K-best decoding"), against the matrix as it was before any reweighting:
     <out>/gretel.kbest    "# N L cond_mode marginal_term S states K n" + one line per rank of the K exactly best haplotypes of the
                           chain likelihood: rank, ll_chain, gap to rank 0, hamming0 (SNPs that differ from rank 0), the i_0 of the
@@ -107,6 +110,9 @@ def build_parser():
                    "(L <= 12 without deletion columns, L <= 10 with them) at a kernel launch per SNP and a byte of device memory per "
                    "SNP and state; with --exact it is what runs" % GRID_MAX_STATES)
     p.add_argument("--margins", action="store_true", help=MARGINS_HELP)
+    p.add_argument("--margins-grid", action="store_true", help="--margins through the grid: the same gretel.margins, for up to %d states, "
+                   "at two kernel launches per SNP and eight bytes of device memory per SNP and state; with --margins it is what "
+                   "runs" % GRID_MAX_STATES)
     p.add_argument("--kbest", type=int, default=None, metavar="K", help=KBEST_HELP)
     p.add_argument("--alternatives", type=int, default=None, metavar="M", help="for the M SNPs whose call is least certain (smallest "
                    "max-marginal gap) decode the best haplotype that carries the runner-up allele there, exactly, on the unreweighted "
@@ -406,14 +412,14 @@ def margins_text(head, i0s, marg, mm, cm, snp_rev):
     return "".join(lines)
 
 
-def write_margins_result(paths, res, head, order, vcf_h, args, name=None):
+def write_margins_result(paths, res, head, order, vcf_h, args, name=None, flag="--margins"):
     """What follows the max-marginals call, for this CLI and for gretel_amd.panel (which makes one call for all its regions): `res`
     is Hansel.viterbi_marginals' dict, `head` the header's six figures (N, L, cond_mode, marginal_term, S, states -- S and states
     as the call left them), `order` the handle's cand_order.  At a hole the note on stderr (behind `name` where there is one)
     and no file; otherwise gretel.margins for the distinct haplotypes in out.fasta's order."""
     from .hansel import margins_of
     if res["hole_at"]:
-        sys.stderr.write("%s[NOTE] --margins: no candidate at SNP %d, no max-marginals\n" % ("%s: " % name if name else "", res["hole_at"]))
+        sys.stderr.write("%s[NOTE] %s: no candidate at SNP %d, no max-marginals\n" % ("%s: " % name if name else "", flag, res["hole_at"]))
         return
     keys = sorted(paths, key=lambda x: paths[x]["i_0"])
     marg = margins_of(res["mm"], res["cm"], _path_array(paths, keys, len(res["cm"]) - 1), order)
@@ -421,26 +427,34 @@ def write_margins_result(paths, res, head, order, vcf_h, args, name=None):
         fh.write(margins_text(head, [paths[k]["i_0"] for k in keys], marg, res["mm"], res["cm"], vcf_h["snp_rev"]))
 
 
-def marginals_once(unweighted):
+def marginals_once(unweighted, grid=False):
     """The one max-marginals call --margins and --alternatives share: (Hansel.viterbi_marginals' dict, (S, states) as the call
-    left them), or (None, the library's refusal)."""
+    left them), or (None, the library's refusal).
+    grid (--margins-grid): the same through Hansel.viterbi_marginals_grid, behind a note of what it allocates."""
+    if grid:
+        s, le, states = unweighted.viterbi_states()
+        if 0 < states <= GRID_MAX_STATES:
+            sys.stderr.write("[NOTE] --margins-grid: S = %d candidate symbols, Le = %d: %d states, %d bytes of device scratch\n"
+                             % (s, le, states, unweighted.viterbi_marginals_grid_bytes()))
     try:
-        res = unweighted.viterbi_marginals()
+        res = unweighted.viterbi_marginals_grid() if grid else unweighted.viterbi_marginals()
     except GretelHipError as e:
         return None, e
-    s, _, states, _ = unweighted.viterbi_info()
+    s, _, states, _ = unweighted.viterbi_grid_info() if grid else unweighted.viterbi_info()
     return res, (s, states)
 
 
 def write_margins(paths, unweighted, vcf_h, args, call=None):
     """--margins: the max-marginals of the copy taken before the spins, read for the distinct haplotypes in out.fasta's order.
     A window beyond the exact decoder's cap: the library's message on stderr and no file.  `call`: marginals_once's pair where
-    the call has been made already."""
-    res, info = call if call is not None else marginals_once(unweighted)
+    the call has been made already.  With args.margins_grid (--margins-grid) the call is the grid's, whose cap is 2^24 states."""
+    grid = getattr(args, "margins_grid", False)                 # (gretel_amd.panel's parser has no --margins-grid)
+    flag = "--margins-grid" if grid else "--margins"
+    res, info = call if call is not None else marginals_once(unweighted, grid=True) if grid else marginals_once(unweighted)
     if res is None:
-        sys.stderr.write("[NOTE] --margins: %s\n" % info)
+        sys.stderr.write("[NOTE] %s: %s\n" % (flag, info))
         return
-    write_margins_result(paths, res, _score_head(unweighted, vcf_h) + info, unweighted._cfg["cand_order"], vcf_h, args)
+    write_margins_result(paths, res, _score_head(unweighted, vcf_h) + info, unweighted._cfg["cand_order"], vcf_h, args, flag=flag)
 
 
 def parse_pin(spec):
@@ -695,7 +709,7 @@ def main(argv=None):
     hansel.snapshot_original()                                                    # cmd.py:79 (what the copy is used for)
     # (the reference's copy of cmd.py:79, made only where something is scored against the matrix as the reads filled it)
     masked = bool(args.alternatives or args.pin)
-    unweighted = hansel.copy() if (args.score_paths or args.known or args.margins or args.kbest or masked) else None
+    unweighted = hansel.copy() if (args.score_paths or args.known or args.margins or args.margins_grid or args.kbest or masked) else None
     if args.dumpmatrix:
         hansel.save_hansel_dump(args.dumpmatrix)                                  # cmd.py:81-82
     if gap_report(hansel, vcf_h):
@@ -720,8 +734,11 @@ def main(argv=None):
         write_scores(paths, unweighted, vcf_h, args)
     if args.known:
         write_known(paths, unweighted, vcf_h, args)
-    marg = marginals_once(unweighted) if (args.margins or args.alternatives) else None      # (one call for the two of them)
-    if args.margins:
+    # (one LDS call for --margins and --alternatives; with --margins-grid the file comes from the grid call, made once)
+    marg = marginals_once(unweighted) if ((args.margins and not args.margins_grid) or args.alternatives) else None
+    if args.margins_grid:
+        write_margins(paths, unweighted, vcf_h, args)
+    elif args.margins:
         write_margins(paths, unweighted, vcf_h, args, call=marg)
     if args.kbest:
         write_kbest(paths, unweighted, vcf_h, args)

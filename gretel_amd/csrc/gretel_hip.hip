@@ -3468,3 +3468,6 @@ static int check_symbol_rows(const uint8_t *paths, int n_paths, size_t n1, int c
 // exact decoding beyond the states two LDS rows hold: the score rows in global memory, one launch per position (gh_viterbi_path_grid,
 // gh_viterbi_spin_grid, gh_viterbi_grid_info)
 #include "viterbi_grid.hpp"
+// ... and the max-marginals there: the step with every row kept, a backward step per position, the maxima per workgroup as it goes
+// (gh_viterbi_marginals_grid)
+#include "viterbi_grid_marg.hpp"

@@ -213,6 +213,40 @@ inline vitg_bufs vitg_layout(void *base, int N, size_t table_doubles, size_t sta
             c.take<int32_t>(parts), c.take<uint8_t>(n1), parts, c.used};
 }
 
+// the max-marginals on the grid (viterbi_grid_marg.hpp), in the exact decoder's block of the handle: `out` and the candidate bytes
+// first under both sizings, exactly as in vitg_layout (the call opens as the grid decoder does).  What grows: ONE KEPT ROW of F
+// per position, N * states doubles (0.5 GB at 60 SNPs and 4^10 states, 4.7 GB at 5^10; it is not bounded by checkpointing), with
+// the one +0.0 of position 0 behind the last row so that every row starts as the part does.  Then the two rows of B, the
+// partial maxima -- five doubles per position and workgroup of GH_VITGM_THREADS threads; a thread owns S consecutive states, and
+// the part is sized for S = 2, the most workgroups a state count can make, so that the layout is a function of N, Le and the
+// state count alone (at S = 5 two fifths of it are used; it is a hundredth of F either way) -- and what goes home.  Every
+// product with `states` or N is formed in size_t.
+#define GH_VITGM_THREADS 256
+
+struct vitgm_bufs {
+    vit_out *out;
+    uint8_t *cm5, *cm0;    // [N + 1] each, k_vit_cands' bytes: what the host reads, and the symbol bits of the opening (not read)
+    double *Gb;
+    double *F;             // [N][states]: row p - 1 belongs to position p; F[N * states] = +0.0, the empty prefix of position 0
+    double *B;             // [2][states]: position p in row p & 1
+    double *part;          // [N][wgs][5]: block p - 1 belongs to position p (a launch fills its first ceil(states / S / 256) entries)
+    double *mm;            // [N + 1][7]
+    uint8_t *cm;           // [N + 1] candidate bits over the seven symbols
+    size_t wgs;
+    size_t total;
+};
+
+inline vitgm_bufs vitgm_layout(void *base, int N, size_t table_doubles, size_t states)
+{
+    scratch_carver c{(char *)base};
+    const size_t n1 = (size_t)N + 1, wgs = (states + 2 * GH_VITGM_THREADS - 1) / (2 * GH_VITGM_THREADS);
+    vit_out *out = c.take<vit_out>(1);
+    uint8_t *cm5 = c.take<uint8_t>(n1), *cm0 = c.take<uint8_t>(n1);
+    if (!states) return {out, cm5, cm0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, c.used};
+    return {out, cm5, cm0, c.take<double>(table_doubles), c.take<double>((size_t)N * states + 1), c.take<double>(2 * states),
+            c.take<double>((size_t)N * wgs * 5), c.take<double>(n1 * GH_NSYM), c.take<uint8_t>(n1), wgs, c.used};
+}
+
 // the exact decoder over a panel (viterbi_panel.hpp), a block of the batch: one descriptor per window (WD = vit_win, which holds
 // device types and so stands in viterbi_panel.hpp), the windows' vit_outs gathered for one copy to the host, and their path rows
 // gathered back to back (`path_bytes` = the sum of N_w + 1)

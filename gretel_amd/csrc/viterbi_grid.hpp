@@ -70,7 +70,9 @@ __device__ __forceinline__ uint32_t vitg_mask(unsigned long long m0, unsigned lo
     return (uint32_t)(k < 12 ? m0 >> (5 * k) : m1 >> (5 * (k - 12))) & 31u;
 }
 
-template <int S>
+// KEEP (viterbi_grid_marg.hpp): the forward pass of the max-marginals on the grid -- the same step, the caller hands it rows of
+// its kept block; no back-pointers (bp is not touched)
+template <int S, bool KEEP = false>
 __global__ void __launch_bounds__(VITG_THREADS)
 k_vitg_step(const double *__restrict__ Gb, int p, int L, int pw, int marginal_term, uint32_t sp, unsigned long long m0, unsigned long long m1,
             uint32_t cm_old, const double *__restrict__ Vc, double *__restrict__ Vn, uint8_t *__restrict__ bp)
@@ -135,7 +137,7 @@ k_vitg_step(const double *__restrict__ Gb, int p, int L, int pw, int marginal_te
             }
         }
         Vn[d * pw + r] = best;
-        bp[d * pw + r] = (uint8_t)arg;
+        if constexpr (!KEEP) bp[d * pw + r] = (uint8_t)arg;
     }
 }
 
@@ -242,20 +244,41 @@ template <typename F> static void vitg_with_S(int S, F &&f)
     }
 }
 
-// one exact decoding of the tensor as it stands on the grid: the path row stays in the handle's scratch (`b`), *ho = hole, score, U
-static int vitg_run(gh_handle *h, vitg_bufs *b, vit_out *ho, const char *who)
+// what a grid call opens with (the decoder here, the max-marginals of viterbi_grid_marg.hpp): the candidate bytes at home, and what
+// the host forms from them
+struct vitg_win {
+    std::vector<uint8_t> cm5;  // [N + 1] candidate bits over the compact indices
+    uint32_t U = 0;
+    uint32_t sp = 0;           // digit -> compact index b5, ascending: the candidate order
+    uint32_t d0 = 0;           // positions <= 0 offer digit 0 alone
+    int S = 0, L = 0;
+    int pw = 0;                // S^(Le-1)
+    int hole = 0;              // the first position that offers nothing: the call ends there
+    int64_t states = 0;
+    uint32_t at(int p) const { return p >= 1 ? (uint32_t)cm5[p] : d0; }
+    // the masks of positions p, p-1, ... p-Le+1 at bits 0, 5, ... of m[0], from the thirteenth on of m[1]; S = 1 has no digits
+    void masks(int p, unsigned long long m[2]) const
+    {
+        m[0] = m[1] = 0;
+        for (int k = 0; k < (S > 1 ? L : 1); k++) m[k / 12] |= (unsigned long long)at(p - k) << (5 * (k % 12));
+    }
+};
+
+// the candidate bytes first: they decide whether the grid serves this window at all.  A hole (w->hole) ends the call before any
+// step is launched and before anything large is reserved; gh_viterbi_grid_info then names the small reservation.
+static int vitg_open(gh_handle *h, vitg_win *w, const char *who)
 {
     const int N = h->N, L = chain_lags(h);
     int rc = ensure_marg(h);                                    // (k_vit_cands reads minfo)
     if (rc) return rc;
-    // the candidate bytes first: they decide whether the decoder serves this window at all
     const size_t small = vitg_layout(nullptr, N, 0, 0).total;
     if ((rc = scratch_reserve(h, &h->vit, small, VITG_SCRATCH))) return rc;
     const vitg_bufs s = vitg_layout(h->vit.buf, N, 0, 0);
     hipLaunchKernelGGL(k_vit_cands, dim3((unsigned)std::min<size_t>(((size_t)N + 256) / 256, 1024)), dim3(256), 0, h->stream,
                        (const double *)h->minfo, N, h->sm, s.cm5, s.cm);
     if ((rc = post_launch(h, "k_vit_cands"))) return rc;
-    std::vector<uint8_t> cm5((size_t)N + 1);
+    std::vector<uint8_t> &cm5 = w->cm5;
+    cm5.assign((size_t)N + 1, 0);
     HIPCHK(hipMemcpyAsync(cm5.data(), s.cm5, (size_t)N + 1, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     uint32_t U = 0;
@@ -265,10 +288,9 @@ static int vitg_run(gh_handle *h, vitg_bufs *b, vit_out *ho, const char *who)
         if (!cm5[p]) hole = p;
     }
     const int S = __builtin_popcount(U);
-    *ho = vit_out{};
-    ho->U = U;
+    w->U = U; w->S = S; w->L = L;
     if (S == 0) {                                             // nothing offered anywhere: the hole is the first position
-        ho->hole_at = 1;
+        w->hole = 1;
         h->vitg_last[0] = 0; h->vitg_last[1] = L; h->vitg_last[2] = 0; h->vitg_last[3] = (int64_t)h->vit.cap;
         return GH_OK;
     }
@@ -281,11 +303,33 @@ static int vitg_run(gh_handle *h, vitg_bufs *b, vit_out *ho, const char *who)
         return fail(GH_ERR_ARG, "%s: S = %d candidate symbols and Le = min(L, N) = %d make %s states, more than the %d the grid decoder "
                     "serves: lower L, or use the beam (--beam, gh_beam_paths)", who, S, L, cnt, GH_VITERBI_GRID_MAX_STATES);
     }
+    w->states = states;
     if (hole) {                                               // the call ends here: no step is launched, nothing else is written
-        ho->hole_at = hole;
+        w->hole = hole;
         h->vitg_last[0] = S; h->vitg_last[1] = L; h->vitg_last[2] = states; h->vitg_last[3] = (int64_t)small;
         return GH_OK;
     }
+    for (int b5 = 0, d = 0; b5 < 5; b5++)
+        if ((U >> b5) & 1u) w->sp |= (uint32_t)b5 << (3 * d++);
+    w->d0 = 1u << (w->sp & 7);
+    w->pw = (int)(states / S);
+    return GH_OK;
+}
+
+// one exact decoding of the tensor as it stands on the grid: the path row stays in the handle's scratch (`b`), *ho = hole, score, U
+static int vitg_run(gh_handle *h, vitg_bufs *b, vit_out *ho, const char *who)
+{
+    const int N = h->N;
+    vitg_win w;
+    int rc = vitg_open(h, &w, who);
+    if (rc) return rc;
+    *ho = vit_out{};
+    ho->U = w.U;
+    ho->hole_at = w.hole;
+    if (w.hole) return GH_OK;
+    const int S = w.S, L = w.L, pw = w.pw;
+    const uint32_t U = w.U, sp = w.sp;
+    const int64_t states = w.states;
     const size_t ns = (size_t)states, table_doubles = (size_t)N * beam_src_doubles(L);
     const size_t need = vitg_layout(nullptr, N, table_doubles, ns).total;
     if ((rc = scratch_reserve(h, &h->vit, need, VITG_SCRATCH))) return rc;
@@ -293,21 +337,11 @@ static int vitg_run(gh_handle *h, vitg_bufs *b, vit_out *ho, const char *who)
     if ((rc = chain_table_build(h, L, b->Gb))) return rc;
     HIPCHK(hipMemsetAsync(b->rows, 0, sizeof(double), h->stream));      // the one prefix at p = 0: every digit 0, score +0.0
 
-    uint32_t sp = 0;                                          // digit -> compact index b5, ascending: the candidate order
-    for (int b5 = 0, d = 0; b5 < 5; b5++)
-        if ((U >> b5) & 1u) sp |= (uint32_t)b5 << (3 * d++);
-    const uint32_t d0 = 1u << (sp & 7);                        // positions <= 0 offer digit 0 alone
-    const int pw = (int)(states / S);                         // S^(Le-1)
-    // the masks of positions p, p-1, ... p-Le+1 at bits 0, 5, ... of m[0], from the thirteenth on of m[1]; S = 1 has no digits
-    auto masks = [&](int p, unsigned long long m[2]) {
-        m[0] = m[1] = 0;
-        for (int k = 0; k < (S > 1 ? L : 1); k++) m[k / 12] |= (unsigned long long)(p - k >= 1 ? (uint32_t)cm5[p - k] : d0) << (5 * (k % 12));
-    };
     const unsigned nb = (unsigned)((pw + VITG_THREADS - 1) / VITG_THREADS);
     unsigned long long m[2];
     for (int p = 1; p <= N; p++) {
-        masks(p, m);
-        const uint32_t cm_old = p - L >= 1 ? (uint32_t)cm5[p - L] : d0;
+        w.masks(p, m);
+        const uint32_t cm_old = w.at(p - L);
         const double *Vc = b->rows + (size_t)((p - 1) & 1) * ns;
         double *Vn = b->rows + (size_t)(p & 1) * ns;
         uint8_t *bp = b->bp + (size_t)p * ns;
@@ -317,7 +351,7 @@ static int vitg_run(gh_handle *h, vitg_bufs *b, vit_out *ho, const char *who)
         });
         if ((rc = post_launch(h, "k_vitg_step"))) return rc;
     }
-    masks(N, m);
+    w.masks(N, m);
     vitg_with_S(S, [&](auto sc) {
         hipLaunchKernelGGL(k_vitg_end<decltype(sc)::value>, dim3((unsigned)b->parts), dim3(VITG_THREADS), 0, h->stream,
                            (const double *)(b->rows + (size_t)(N & 1) * ns), (int)states, L, sp, m[0], m[1], b->pv, b->pj);

@@ -188,6 +188,25 @@ def grid_scratch_bytes(n, le, states):
     return head + up(n * (30 * le + 6) * 8) + up(n1 * states) + up(16 * states) + up(8 * parts) + up(4 * parts) + up(n1)
 
 
+def grid_marginals_scratch_bytes(n, le, states):
+    """vitgm_layout's total (gretel_amd/csrc/scratch_layout.hpp) for a window of n SNPs, Le lags and `states` states: what the
+    max-marginals on the grid reserve.  Host only.  Every part starts on a 256-byte boundary: grid_scratch_bytes' first three
+    parts and the table, then one kept row of F per position (n * states doubles and the one +0.0 of position 0), two rows of B,
+    five partial maxima per position and 512 states, mm [n + 1][7] and cm [n + 1].  0 beyond the grid's cap; no states leaves
+    the first three parts."""
+    def up(x):
+        return (x + 255) & ~255
+    if states > _lib.GH_VITERBI_GRID_MAX_STATES:
+        return 0
+    n1 = int(n) + 1
+    head = up(24) + 2 * up(n1)
+    if states < 1:
+        return head
+    wgs = (states + 511) // 512
+    return (head + up(n * (30 * le + 6) * 8) + up((n * states + 1) * 8) + up(16 * states) + up(n * wgs * 5 * 8) + up(n1 * 7 * 8)
+            + up(n1))
+
+
 def allow_of(n, pins=None, bans=None):
     """One constraint set of Hansel.viterbi_path_masked for a window of n SNPs: uint8[n+1], all 0x7f (everything allowed) except
     where given.  Host only.  pins {p: symbols}: only these are allowed at SNP p; bans {p: symbols}: these are not (a ban on a
@@ -688,6 +707,28 @@ class Hansel:
         is beyond the grid decoder's cap.  Host arithmetic over viterbi_states(): vitg_layout of gretel_amd/csrc/scratch_layout.hpp."""
         _, le, states = self.viterbi_states()
         return grid_scratch_bytes(self.n, le, states)
+
+    def viterbi_marginals_grid(self):
+        """viterbi_marginals() on the grid (gh_viterbi_marginals_grid; INTEGRATION.md "Max-marginals on the grid"): the same
+        definition and the same dict, equal as IEEE values where both serve a window, for up to 2^24 states -- one kept row of F
+        per SNP in device memory, two launches per SNP.  Always the grid kernels, whatever the state count;
+        viterbi_marginals_grid_bytes() says beforehand what it reserves, viterbi_grid_info() afterwards describes the call.  The
+        tensor is not touched."""
+        self._ensure()
+        mm = np.full((self.n + 1, 7), -np.inf)
+        cm = np.zeros(self.n + 1, dtype=np.uint8)
+        hole = C.c_int()
+        check(self._lib.gh_viterbi_marginals_grid(self._h, _p(mm), _p(cm), C.byref(hole)))
+        if hole.value:
+            return dict(mm=None, cm=None, hole_at=hole.value)
+        return dict(mm=mm, cm=cm, hole_at=0)
+
+    def viterbi_marginals_grid_bytes(self):
+        """The device scratch viterbi_marginals_grid() reserves on the tensor as it stands where it meets no hole, and 0 where the
+        window is beyond the grid's cap.  Host arithmetic over viterbi_states(): vitgm_layout of
+        gretel_amd/csrc/scratch_layout.hpp."""
+        _, le, states = self.viterbi_states()
+        return grid_marginals_scratch_bytes(self.n, le, states)
 
     def clear(self):
         self._staged = []

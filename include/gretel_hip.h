@@ -417,6 +417,23 @@ int gh_viterbi_grid_info(const gh_t *h, int64_t out[4]);
  * following gh_spin stay as they are, bit for bit.  gh_viterbi_info afterwards describes this call: S, Le, states, scratch bytes. */
 int gh_viterbi_marginals(gh_t *h, double *mm /*[N+1][7]*/, uint8_t *cm /*[N+1]*/, int *hole_at);
 
+/* Max-marginals on the grid (INTEGRATION.md "Max-marginals on the grid"): gh_viterbi_marginals under the grid decoder's cap.  The
+ * definition is the one above, word for word -- F, B, M, the association of every addition, the output, the hole rule, the
+ * exactness paragraph -- so where both calls serve a window mm, cm and hole_at are equal as IEEE values, -inf included, under
+ * every spec and candidate order, and  max_c mm[N][c] == gh_viterbi_path_grid's ll_chain  exactly.  What differs is where the
+ * dynamic programme lives: one kept row of F per position and two rows of B in device memory, one launch per position each way
+ * on the handle's stream, the maxima taken per workgroup inside the backward step and by one launch at the end.  No workgroup
+ * waits for another; the launch boundary is the only synchronisation.  Always the grid kernels, also on a window of 64 states.
+ * The refusals are gh_viterbi_path_grid's: GH_ERR_ARG for a null argument, offer_zero, or S^Le > GH_VITERBI_GRID_MAX_STATES (the
+ * same message: S, Le, the count, the cap; nothing is allocated for such a window).  GH_ERR_STATE before any fill.  GH_ERR_NOMEM
+ * names the bytes.  A hole is found on the host, from the candidate bits, before anything large is reserved or any step launched.
+ * The scratch is the exact decoder's block of the handle, kept until gh_destroy: the table, N * S^Le * 8 bytes of F (it is not
+ * bounded by checkpointing), 16 * S^Le bytes of B, five partial maxima per position and 512 states, mm and cm -- 525 160 704 bytes
+ * at 60 SNPs and 4^10 states, 4 889 679 360 at 5^10; 2 558 689 024 and 23 823 391 488 at 300 SNPs: ask gh_viterbi_states first.
+ * It only reads the tensor; gh_viterbi_grid_info afterwards describes this call (S, Le, states, bytes reserved); gh_viterbi_info is
+ * not touched. */
+int gh_viterbi_marginals_grid(gh_t *h, double *mm /*[N+1][7]*/, uint8_t *cm /*[N+1]*/, int *hole_at);
+
 /* K-best exact decoding of the chain likelihood (no reference counterpart; INTEGRATION.md "K-best decoding").  gh_viterbi_path says
  * what the best full path is and gh_viterbi_marginals how much every other choice would cost; this returns the runner-up paths
  * themselves: the k full paths of largest score, exactly.  Notation as in "Exact decoding" above; a state at p is the last
